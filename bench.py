@@ -32,6 +32,15 @@ What the line carries beyond the contract fields:
   cpu_baseline       (N = 1) the CPU oracle on all host threads, on a bounded sample of the workload
 Counter-derived fields (`traffic`, `valu`) come from committed rocprofv3 passes (profiles/<round>_pmc_*.json) and are emitted only
 when those passes were made on the very kernel sources this run loads (hash of pinocchio_amd/csrc); otherwise null.
+
+A plain run sets up, warms up, times the steps and prints the line: roofline, roofline_by_class, path_roofline and kernels then come
+from the HIP events of the timed region alone.  What takes measurements or runs of its own -- hbm_streaming, the in-line pass behind
+kernel_table, exact_libm, cpu_baseline, boundary, result_check, and at 2 and 4 ranks exchange.alternative -- comes with --full:
+
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs), so that two builds can be compared
+output for output on the same inputs.
 """
 from __future__ import annotations
 
@@ -262,28 +271,44 @@ def parse_args(argv=None):
     ap.add_argument("--ns", type=int, default=12, help="number of smoothing radii")
     ap.add_argument("--field-bytes", type=int, default=8, choices=(4, 8))
     ap.add_argument("--no-lpt", action="store_true", help="Fmax-only (BASELINE config 2)")
-    ap.add_argument("--cpu-n", type=int, default=512, help="grid side of the CPU-baseline sample (0: skip)")
-    ap.add_argument("--exact-steps", type=int, default=1, help="steps of the PF_EXACT_LIBM=1 informational run (0: skip)")
-    ap.add_argument("--table-steps", type=int, default=2,
-                    help="steps of the in-line pass the per-kernel table comes from when the timed configuration overlaps kernels (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the line can carry beyond the headline figure: the result check, the streaming rates, the boundary "
+                         "hand-off, the in-line pass for the per-kernel table, the exact-libm run, the CPU baseline and (2 and 4 ranks) the "
+                         "other delta(k) mode.  Without it a run sets up, warms up, times the steps and prints the line; the options "
+                         "below whose default depends on --full can still switch one part on or off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--cpu-n", type=int, default=None, help="grid side of the CPU-baseline sample (0: skip; default 512 with --full, else 0)")
+    ap.add_argument("--exact-steps", type=int, default=None,
+                    help="steps of the PF_EXACT_LIBM=1 informational run (0: skip; default 1 with --full, else 0)")
+    ap.add_argument("--table-steps", type=int, default=None,
+                    help="steps of the in-line pass the per-kernel table comes from when the timed configuration overlaps kernels "
+                         "(0: skip; default 2 with --full, else 0)")
     ap.add_argument("--exchange", default="rccl", choices=("rccl", "torch"))
-    ap.add_argument("--replicate", default="both", choices=("auto", "0", "1", "both"),
+    ap.add_argument("--replicate", default=None, choices=("auto", "0", "1", "both"),
                     help="(N > 1) delta(k) kept whole on every rank (1), exchanged for every transform (0), the library's choice by rank "
-                         "count (auto), or -- at 2 and 4 ranks -- the library's choice timed as the line plus the other mode timed "
-                         "beside it in exchange.alternative (both, the default: one run decides DESIGN.md section 5's model)")
+                         "count (auto, the default), or -- at 2 and 4 ranks -- the library's choice timed as the line plus the other mode "
+                         "timed beside it in exchange.alternative (both, the default with --full: one run decides DESIGN.md section 5's model)")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo-host"),
                     help="nccl (= RCCL): one rank per GPU, the measurement.  gloo-host: a bring-up path for boxes with ONE GPU -- gloo process "
                          "group, every rank on device 0, exchanges staged through host memory (pinocchio_amd/dist.py HostStagedKind): it "
                          "exercises this script's multi-rank code end to end (tests/test_gpu_gloo_ranks.py); its numbers mean nothing")
-    ap.add_argument("--check", type=int, default=1,
-                    help="1: after the timed region, fingerprint Fmax / Rmax / the displacements and compare with the single-GPU golden of the configuration (tests/golden/bench_fingerprints.json)")
-    ap.add_argument("--boundary", type=int, default=1,
-                    help="1 (one GPU): after the timed region, time the hand-off itself -- pf_get_products, pf_update_products, pf_set_density -- and print it as `boundary`")
+    ap.add_argument("--check", type=int, default=None,
+                    help="1: after the timed region, fingerprint Fmax / Rmax / the displacements and compare with the single-GPU golden of the "
+                         "configuration (tests/golden/bench_fingerprints.json; default 1 with --full, else 0)")
+    ap.add_argument("--boundary", type=int, default=None,
+                    help="1 (one GPU): after the timed region, time the hand-off itself -- pf_get_products, pf_update_products, pf_set_density -- "
+                         "and print it as `boundary` (default 1 with --full, else 0)")
     ap.add_argument("--slab-of", type=int, default=0,
                     help="P > 1: time the kernels of ONE rank of a P-rank run of the n^3 box on this GPU, exchange short-circuited (see run_slab)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher check: every rank prints its RANK / LOCAL_RANK / WORLD_SIZE as a JSON line and exits; nothing touches a GPU")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    for name, full, plain in (("cpu_n", 512, 0), ("exact_steps", 1, 0), ("table_steps", 2, 0), ("replicate", "both", "auto"),
+                              ("check", 1, 0), ("boundary", 1, 0)):
+        if getattr(args, name) is None:
+            setattr(args, name, full if args.full else plain)
+    return args
 
 
 def gpu_untouched() -> bool:
@@ -383,11 +408,59 @@ def fingerprint_key(n: int, ns: int, lpt: bool, fb: int) -> str:
     return f"n{n}_ns{ns}_{'lpt' if lpt else 'fmax'}_fb{fb}"
 
 
-def run_config(args, rank, world, device, dist, torch, replicate_env, votes_out, solve_inline=False):
+DUMP_SAMPLE = 1 << 19        # cells a larger box is dumped on: 36 MB with the LPT part and the index
+DUMP_SEED = 0x5EED_F4A7
+
+
+def dump_sample_index(n: int) -> np.ndarray:
+    """global cell indices (x-major) whose products --dump-outputs writes: every cell of a box of up to DUMP_SAMPLE cells, else a
+    fixed, seeded draw of them -- the same for every run, build and rank count"""
+    if n ** 3 <= DUMP_SAMPLE:
+        return np.arange(n ** 3, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n ** 3, size=DUMP_SAMPLE, dtype=np.int64))
+
+
+def dump_outputs(out_dir: str, f, tv, rank: int, world: int, dist, lpt: bool):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step -- the TrueVariance per radius that compute_fmax
+    returns (true_variance.npy) and the product columns it reads from the context (Fmax, Rmax, and with the LPT part Vel, Vel_2LPT,
+    Vel_3LPT_1, Vel_3LPT_2) on the cells of dump_sample_index (sample_index.npy): float32 as the products hold them, Rmax and the
+    indices as float64 (exact).  Every rank reads its own slab, one column at a time through one host buffer; rank 0 writes."""
+    cells = f.nxl * f.n * f.n
+    idx = dump_sample_index(f.n)
+    first = rank * cells                              # x-slabs: global index = rank * cells + local
+    mine = idx[(idx >= first) & (idx < first + cells)] - first
+    cols = [("FMAX", "Fmax"), ("RMAX", "Rmax")]
+    if lpt:
+        cols += [("ZEL ", "Vel"), ("2LPT", "Vel_2LPT"), ("31PT", "Vel_3LPT_1"), ("32PT", "Vel_3LPT_2")]
+    buf = np.empty((cells, 3) if lpt else cells, dtype=np.float32)
+    part = {}
+    for block, name in cols:
+        f._chk(f.L.pf_get_block(f.h, block.encode(), 4, buf.ctypes.data_as(C.c_void_p)))
+        if block == "FMAX":
+            part[name] = buf.reshape(-1)[:cells][mine].copy()
+        elif block == "RMAX":
+            part[name] = buf.reshape(-1)[:cells].view(np.int32)[mine].astype(np.float64)
+        else:
+            part[name] = buf[mine].copy()
+    del buf
+    parts = [part]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, part)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "true_variance.npy"), np.asarray(tv, dtype=np.float64))
+        np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+        for _, name in cols:
+            np.save(os.path.join(out_dir, name + ".npy"), np.concatenate([p[name] for p in parts]))
+
+
+def run_config(args, rank, world, device, dist, torch, replicate_env, votes_out, solve_inline=False, dump_dir=None):
     """One timed configuration on this rank: context, exchange, warm-up, exactly `steps` timed steps between fences.
     replicate_env: None (the library's choice) or "0" / "1" for PF_REPLICATE_DK, read by pf_create.
     solve_inline: PF_SOLVE_BESIDE_Z=0 for this context -- every kernel in line on one stream, so that the HIP-event spans of
     the kernels do not overlap (the pass the per-kernel table comes from; never the timed configuration).
+    dump_dir: --dump-outputs of the line's configuration, written before anything else reads the products.
     -> dict of what rank 0 prints (every rank returns its own; only rank 0's is used)"""
     from pinocchio_amd import api, synth
     n, ns, lpt = args.n, args.ns, not args.no_lpt
@@ -464,6 +537,8 @@ def run_config(args, rank, world, device, dist, torch, replicate_env, votes_out,
             t = torch.tensor([dt], dtype=torch.float64, device="cpu" if args.backend == "gloo-host" else "cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
+        if dump_dir:
+            dump_outputs(dump_dir, f, tv, rank, world, dist, lpt)
         # what the timed steps left in `products`, after the timed region: exact fingerprints (and the Fmax histogram), to be held
         # against those of a single-GPU run of the same configuration -- a decomposition that moves a block to the wrong place
         # still runs at full speed
@@ -485,7 +560,7 @@ def run_config(args, rank, world, device, dist, torch, replicate_env, votes_out,
         res["check"] = check
         # streaming yardsticks of this box and process, after the timed region: a kernel that only reads / writes / copies a field
         stream = None
-        if world == 1 and not (n & (n - 1)):
+        if world == 1 and not (n & (n - 1)) and args.full:
             stream = {}
             v = C.c_double()
             for kind, name in ((0, "read_GBps"), (1, "write_GBps"), (2, "copy_GBps")):
@@ -829,6 +904,8 @@ def main():
     if args.slab_of > 1:
         if world != 1:
             raise SystemExit("--slab-of runs on one GPU")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: a --slab-of run computes no box's products")
         return run_slab(args)
 
     dist = torch = None
@@ -861,7 +938,7 @@ def main():
     votes = []
     modes = [None if args.replicate in ("auto", "both") else args.replicate]
     try:
-        res = run_config(args, rank, world, device, dist, torch, modes[0], votes)
+        res = run_config(args, rank, world, device, dist, torch, modes[0], votes, dump_dir=args.dump_outputs)
         alt = None
         if world in (2, 4) and args.replicate == "both":
             # the other way of feeding the x-pass, same steps, same fences: the line is the library's

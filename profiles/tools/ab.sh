@@ -4,6 +4,7 @@
 # Writes gpurun_out/ab_<name>.json; extra bench arguments through AB_ARGS.
 cd "$(dirname "$0")/../.." || exit 1
 mkdir -p gpurun_out
+AB_ARGS="--full $AB_ARGS"   # the per-kernel table of the in-line pass is part of bench.py --full
 for v in "$@"; do
   lib=pinocchio_amd/csrc/build_$v/libpinfmax_hip_$v.so
   [ "$v" = default ] && lib=pinocchio_amd/libpinfmax_hip.so

@@ -2,6 +2,7 @@
 # A/B of environment settings on one box: ab_envs.sh "name1:VAR=a VAR2=b" "name2:VAR=c" ...   (name "base:" = no variables)
 cd "$(dirname "$0")/../.." || exit 1
 mkdir -p gpurun_out
+AB_ARGS="--full $AB_ARGS"   # the per-kernel table of the in-line pass is part of bench.py --full
 names=()
 for spec in "$@"; do
   name=${spec%%:*}; vars=${spec#*:}

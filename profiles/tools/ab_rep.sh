@@ -2,6 +2,7 @@
 # replicated A/B: ab_rep.sh REPS "name:VARS" ...  -> interleaved runs, per-class ms per launch as mean (min..max)
 cd "$(dirname "$0")/../.." || exit 1
 mkdir -p gpurun_out
+AB_ARGS="--full $AB_ARGS"   # the per-kernel table of the in-line pass is part of bench.py --full
 reps=$1; shift
 for r in $(seq 1 $reps); do
   for spec in "$@"; do

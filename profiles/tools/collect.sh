@@ -10,6 +10,7 @@
 # 5. the default bench line (python3 bench.py), which then carries the counters of step 3.
 # The profiled program is `python3 bench.py ...` directly after `--` (no env / bash -c hop: the profiler has initialised the GPU).
 tag=${1:-r02}
+BENCH_ARGS="--full $BENCH_ARGS"   # the in-line pass, the streaming rates and the default line's other parts are bench.py --full
 R=$PWD
 export TMPDIR=/tmp
 mkdir -p gpurun_out

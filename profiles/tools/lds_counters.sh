@@ -4,6 +4,7 @@
 # the profiled program is `python3 bench.py ...` directly after `--`.  Output: gpurun_out/pmc_<tag>_lds*/ and, through
 # profiles/tools/summarise_lds.py, gpurun_out/<tag>_pmc_lds.json (copy into profiles/ to commit).
 tag=${1:-r03}
+BENCH_ARGS="--full $BENCH_ARGS"   # the same step and extras as before bench.py had a lean default
 R=$PWD
 export TMPDIR=/tmp
 export PF_SOLVE_BESIDE_Z=0  # every kernel in line, as in the counter passes of collect.sh (the same kernels doing the same work)

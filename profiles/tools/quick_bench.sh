@@ -1,6 +1,7 @@
 #!/bin/bash
 # quick look at a build ON THE GPU BOX: a short default-order bench (no CPU baseline, no exact-libm run) and its per-kernel table
 tag=${1:-quick}; shift
+set -- --full "$@"   # the per-kernel table of the in-line pass is part of bench.py --full
 mkdir -p gpurun_out/r04
 timeout 600 python3 bench.py --steps 3 --warmup 1 --cpu-n 0 --exact-steps 0 "$@" > gpurun_out/r04/bench_$tag.json 2> gpurun_out/r04/bench_$tag.err
 python3 - "$tag" <<'PY'

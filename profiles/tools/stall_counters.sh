@@ -3,6 +3,7 @@
 # Each group is its own rocprofv3 run with --kernel-trace only; only counters the installed rocprofv3 lists are asked for.
 # Output: gpurun_out/pmc_<tag>_stall*/ and gpurun_out/<tag>_pmc_stall.json (copy into profiles/ to commit).
 tag=${1:-r04}
+BENCH_ARGS="--full $BENCH_ARGS"   # the same step and extras as before bench.py had a lean default
 R=$PWD
 export TMPDIR=/tmp
 export PF_SOLVE_BESIDE_Z=0

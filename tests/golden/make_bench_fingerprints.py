@@ -27,7 +27,7 @@ def main():
     for n, ns, lpt, fb in CONFIGS:
         if only and n not in only:
             continue
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n", str(n), "--ns", str(ns), "--steps", "1", "--warmup", "0", "--cpu-n", "0",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n", str(n), "--ns", str(ns), "--steps", "1", "--warmup", "0", "--full", "--cpu-n", "0",
                "--exact-steps", "0", "--table-steps", "0", "--field-bytes", str(fb)] + ([] if lpt else ["--no-lpt"])
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode:

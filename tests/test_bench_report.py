@@ -182,3 +182,26 @@ def test_exchange_report_per_field_and_per_link_numbers():
         assert m["step_ms_if_exchanges_hide"] <= m["step_ms_if_nothing_hides"] and m["compute_ms_per_step_per_rank_on_one_gpu"] > 0
     one = bench.exchange_report(dict(res, stats=stats[:2]), args, P)   # a sweep that exchanged nothing: no per-field numbers, no division by zero
     assert one["calls_per_step"] == 0 and "per_transposed_field" not in one
+
+
+def test_plain_run_leaves_the_extras_to_full():
+    """a plain run only times the steps: every part that measures or checks something of its own is off unless --full (or its own
+    option) asks for it; --full restores the defaults the line had before it became lean"""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert not plain.full and plain.steps == 4 and plain.warmup == 2 and plain.dump_outputs is None
+    assert (plain.cpu_n, plain.exact_steps, plain.table_steps, plain.replicate, plain.check, plain.boundary) == (0, 0, 0, "auto", 0, 0)
+    full = bench.parse_args(["--full"])
+    assert (full.cpu_n, full.exact_steps, full.table_steps, full.replicate, full.check, full.boundary) == (512, 1, 2, "both", 1, 1)
+    mixed = bench.parse_args(["--full", "--cpu-n", "0", "--check", "0", "--dump-outputs", "out"])
+    assert mixed.cpu_n == 0 and mixed.check == 0 and mixed.exact_steps == 1 and mixed.dump_outputs == "out"
+    assert bench.parse_args(["--table-steps", "3"]).table_steps == 3
+
+
+def test_dump_sample_is_fixed_and_covers_small_boxes_whole():
+    """--dump-outputs: the cells of a large box are the same seeded sample in every run (sorted, distinct, inside the box, within the
+    64 MB the dump may take); a small box is written whole"""
+    a, b = bench.dump_sample_index(1024), bench.dump_sample_index(1024)
+    assert np.array_equal(a, b) and np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 1024 ** 3
+    assert 0.99 * bench.DUMP_SAMPLE < a.size <= bench.DUMP_SAMPLE
+    assert a.size * (8 + 4 + 8 + 4 * 12) < 64 << 20          # index, Fmax, Rmax, four displacement vectors
+    assert np.array_equal(bench.dump_sample_index(64), np.arange(64 ** 3))

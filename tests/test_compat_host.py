@@ -133,9 +133,10 @@ def test_geometry_refuses_what_the_path_does_not_do(lib, capfd):
     assert lib.set_one_grid(0) == 0
 
 
-def test_dump_and_read_products_round_trip_and_formats(lib, tmp_path, capfd):
+def test_dump_and_read_products_round_trip_and_formats(lib, tmp_path, capfd, monkeypatch):
     """dump_products / read_dumps (src/fmax.c:372-506) need no device: byte formats of the three files, the round trip, and
     the reference's messages when the dump belongs to another run"""
+    monkeypatch.chdir(tmp_path)   # DumpDir is a char[100]: a relative path, whatever the length of the temporary directory's
     n = 8
     grid = C.cast(C.c_void_p.in_dll(lib, "MyGrids"), C.POINTER(Grid)).contents
     for i in range(3):
@@ -144,7 +145,7 @@ def test_dump_and_read_products_round_trip_and_formats(lib, tmp_path, capfd):
     grid.BoxSize = 16.0
     assert lib.set_one_grid(0) == 0
     par = Params.in_dll(lib, "params")
-    par.DumpDir = (str(tmp_path) + "/dump/").encode()
+    par.DumpDir = b"dump/"
     par.RandomSeed = 486604
     for i in range(3):
         par.GridSize[i] = n
@@ -215,7 +216,7 @@ def test_in_tree_build_of_the_adapter_type_checks(flags):
 
 
 @pytest.mark.gpu
-def test_compute_fmax_like_the_reference_driver(lib, tmp_path):
+def test_compute_fmax_like_the_reference_driver(lib, tmp_path, monkeypatch):
     n = 32
     cell = 2.0                                     # Mpc per cell
     dk = np.ascontiguousarray(synth.make_density(n, seed=synth.SEED))
@@ -254,7 +255,8 @@ def test_compute_fmax_like_the_reference_driver(lib, tmp_path):
         C.c_void_p.in_dll(lib, name).value = C.cast(fn, C.c_void_p).value
     par = Params.in_dll(lib, "params")
     par.RunFlag = b"pftest"
-    par.DumpDir = (str(tmp_path) + "/").encode()
+    monkeypatch.chdir(tmp_path)   # DumpDir is a char[100]: a relative path, whatever the length of the temporary directory's
+    par.DumpDir = b"./"
     par.GridSize[0] = par.GridSize[1] = par.GridSize[2] = n
     par.RandomSeed = synth.SEED
 

@@ -87,7 +87,7 @@ def test_bench_multi_rank_line_end_to_end_on_one_gpu():
     fields must be there and must tell the truth (two ranks in the communicator, ONE distinct device, hence n_gpus 1 and a warning)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "PF_REPLICATE_DK")}
     r = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--n", "64", "--ns", "4", "--steps", "1",
-                        "--warmup", "1", "--backend", "gloo-host", "--cpu-n", "0", "--exact-steps", "0"],
+                        "--warmup", "1", "--backend", "gloo-host", "--full", "--cpu-n", "0", "--exact-steps", "0"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -119,7 +119,7 @@ def test_bench_eight_ranks_exchange_every_transform_on_one_gpu():
     transform goes through the pipelined all-to-all, delta(k) stays distributed) and `--replicate both` has nothing to add"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "PF_REPLICATE_DK")}
     r = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "8", "--n", "64", "--ns", "3", "--steps", "1",
-                        "--warmup", "1", "--backend", "gloo-host", "--cpu-n", "0", "--exact-steps", "0"],
+                        "--warmup", "1", "--backend", "gloo-host", "--full", "--cpu-n", "0", "--exact-steps", "0"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
