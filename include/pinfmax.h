@@ -308,6 +308,25 @@ int pf_update_products(pf_ctx *ctx, void *products_host, const pf_product_layout
    (src/pinocchio.h:84-85).  *count receives the number selected; the first min(*count, capacity) entries are
    copied (either array may be NULL). */
 int pf_select_sorted(pf_ctx *ctx, float flast, size_t capacity, unsigned int *cell_index, float *fmax, size_t *count);
+/* The next step of fragmentation on the device: count_peaks (src/fragment.c:605-706, default non-CLASSIC_FRAGMENTATION form).
+   A cell is stored when Fmax >= flast (a double, as outputs.Flast; src/distribute.c:695); a stored cell is a peak when its
+   Fmax is strictly larger than that of each of its six grid neighbours that is stored too (two equal neighbours are both no
+   peak; NaN is never stored and vetoes nothing).  Region: a sub-box start[3], len[3] in global grid coordinates (x, y, z;
+   wrapping around the periodic box) with the safety layer safe[3] of the reference's subbox.  A direction with len == n is
+   periodic (subbox.pbc); in any other the two border layers are skipped (:630-635).  Well resolved: safe[d] <= i_d <
+   len[d] - safe[d] in the region's own coordinates (:691-694). */
+typedef struct { int start[3], len[3], safe[3]; } pf_peak_region;   /* NULL = the whole periodic box */
+/* peaks[0] = all peaks of the region, peaks[1] = those in its well resolved part, summed over ranks (the reference logs
+   "Task %d found %d peaks, %d in the well resolved region").  Slabs: the planes next to the slab come from the neighbouring
+   ranks through the installed pf_alltoall_fn (a block of two planes per peer), the sums through pf_allreduce_fn.
+   Collective: every rank passes the same flast and region.
+   Products of either precision. */
+int pf_count_peaks(pf_ctx *ctx, double flast, const pf_peak_region *region, unsigned long long peaks[2]);
+/* this rank's peaks of the whole box in index_compare_F order (the order in which fragmentation opens the groups);
+   conventions of pf_select_sorted (local cell index, *count, capacity); fp32 products only */
+int pf_select_peaks(pf_ctx *ctx, double flast, size_t capacity, unsigned int *cell_index, float *fmax, size_t *count);
+/* test tap without a context: the same kernel on a caller's n^3 fp32 field (host, index z + n*(y + n*x)) */
+int pf_debug_peaks(int n, const float *fmax_host, double flast, const pf_peak_region *region, unsigned long long peaks[2]);
 /* Per-particle payload of one block of the "timeless snapshot" (write_timeless_snapshot, src/write_snapshot.c:207-342)
    for this rank's slab, from the SoA columns in HBM: name = "ID  " (1 + global index as MYIDTYPE of id_bytes = 4 or 8,
    :648-664), "FMAX" float, "RMAX" int, "ZEL " / "2LPT" / "31PT" / "32PT" float[3] per particle (:700-855). */

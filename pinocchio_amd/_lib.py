@@ -41,6 +41,10 @@ class CpuTime(C.Structure):
                 ("lpt", C.c_double), ("mem_transf", C.c_double)]
 
 
+class PeakRegion(C.Structure):
+    _fields_ = [("start", C.c_int * 3), ("len", C.c_int * 3), ("safe", C.c_int * 3)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -90,6 +94,9 @@ PROTOTYPES = {
     "pf_derivative": (C.c_int, [_vp, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "pf_select_sorted": (C.c_int, [_vp, C.c_float, C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_float), C.POINTER(C.c_size_t)]),
     "pf_get_block": (C.c_int, [_vp, C.c_char_p, C.c_int, _vp]),
+    "pf_count_peaks": (C.c_int, [_vp, C.c_double, C.POINTER(PeakRegion), C.POINTER(C.c_ulonglong)]),
+    "pf_select_peaks": (C.c_int, [_vp, C.c_double, C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_float), C.POINTER(C.c_size_t)]),
+    "pf_debug_peaks": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_double, C.POINTER(PeakRegion), C.POINTER(C.c_ulonglong)]),
     "pf_set_collapse_model": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "pf_set_modified_gravity": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "pf_set_tabulated_ct": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),

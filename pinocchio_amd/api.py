@@ -41,6 +41,28 @@ def plan_bytes(n: int, nranks: int = 1, field_bytes: int = 8, double_products: b
     return a.value, b.value
 
 
+def _region(region):
+    """None (the whole periodic box) or (start[3], len[3], safe[3]) in global grid coordinates (x, y, z) -> pf_peak_region"""
+    if region is None:
+        return None
+    start, length, safe = region
+    return _lib.PeakRegion((C.c_int * 3)(*map(int, start)), (C.c_int * 3)(*map(int, length)), (C.c_int * 3)(*map(int, safe)))
+
+
+def debug_peaks(fmax: np.ndarray, flast: float, region=None):
+    """count_peaks (src/fragment.c:605-706) by the device kernel on a caller's [n][n][n] fp32 field -> (npeaks, ngood)"""
+    L = _lib.load()
+    f = np.ascontiguousarray(fmax, dtype=np.float32)
+    n = f.shape[0]
+    if f.shape != (n, n, n):
+        raise ValueError(f"field shape {f.shape}")
+    rg = _region(region)
+    out = (C.c_ulonglong * 2)()
+    if L.pf_debug_peaks(n, f.ctypes.data_as(C.POINTER(C.c_float)), float(flast), C.byref(rg) if rg is not None else None, out):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_peaks failed")
+    return int(out[0]), int(out[1])
+
+
 class Fmax:
     """One rank's context: an x-slab of an n^3 grid on one MI355X."""
 
@@ -240,6 +262,25 @@ class Fmax:
         if cnt.value:
             self._chk(self.L.pf_select_sorted(self.h, flast, cnt.value, idx.ctypes.data_as(C.POINTER(C.c_uint)),
                                               f.ctypes.data_as(C.POINTER(C.c_float)), C.byref(cnt)))
+        return idx, f
+
+    def count_peaks(self, flast: float, region=None):
+        """count_peaks (src/fragment.c:605-706): (peaks of the region, those in its well resolved part), summed over ranks.
+        region = (start[3], len[3], safe[3]) in global grid coordinates, None = the whole periodic box.  Collective."""
+        rg = _region(region)
+        out = (C.c_ulonglong * 2)()
+        self._chk(self.L.pf_count_peaks(self.h, float(flast), C.byref(rg) if rg is not None else None, out))
+        return int(out[0]), int(out[1])
+
+    def select_peaks(self, flast: float):
+        """this rank's peaks of the whole box by descending Fmax, ties by ascending index -> (local index, Fmax).  Collective."""
+        cnt = C.c_size_t()
+        # one call with room for every cell of the slab would do; two calls keep the host arrays at the size of the list
+        self._chk(self.L.pf_select_peaks(self.h, float(flast), 0, None, None, C.byref(cnt)))
+        idx = np.empty(cnt.value, dtype=np.uint32)
+        f = np.empty(cnt.value, dtype=np.float32)
+        self._chk(self.L.pf_select_peaks(self.h, float(flast), cnt.value, idx.ctypes.data_as(C.POINTER(C.c_uint)),
+                                         f.ctypes.data_as(C.POINTER(C.c_float)), C.byref(cnt)))
         return idx, f
 
     def block(self, name: str, id_bytes: int = 4) -> np.ndarray:

@@ -69,13 +69,13 @@ extern "C" const char *pf_last_error(void) { return g_err; }
 enum {
   KS_XPASS_HESS = 0, KS_YPASS_HESS, KS_ZPASS_HESS, KS_COLLAPSE, KS_LPT_SRC, KS_LPT_ACC, KS_R2C_Z, KS_YPASS_FWD,
   KS_XPASS_FWD, KS_XPASS_DISP, KS_YPASS_DISP, KS_ZPASS_DISP, KS_XPASS_PLAIN, KS_YPASS_PLAIN, KS_ZPASS_PLAIN,
-  KS_EXCHANGE, KS_MISC, KS_ZCOLLAPSE, KS_ZPASS_INV, KS_COLLAPSE_INV, KS_ZPASS_LPT3B, KS_COLLAPSE_SRC, KS_COUNT
+  KS_EXCHANGE, KS_MISC, KS_ZCOLLAPSE, KS_ZPASS_INV, KS_COLLAPSE_INV, KS_ZPASS_LPT3B, KS_COLLAPSE_SRC, KS_PEAKS, KS_COUNT
 };
 static const char *ks_names[KS_COUNT] = {
     "xpass_hess_1to3", "ypass_hess_3to6", "zpass_c2r_hess_6", "collapse", "lpt_sources", "lpt_accum", "zpass_r2c",
     "ypass_fwd", "xpass_fwd", "xpass_disp_1to2", "ypass_disp_2to3", "zpass_c2r_disp_3", "xpass_plain", "ypass_plain",
     "zpass_c2r_plain", "exchange", "misc", "zpass_collapse_fused", "zpass_c2r_hess_6to3inv", "collapse_inv", "zpass_c2r_hess_6_lpt3b",
-    "collapse_lpt_sources"};
+    "collapse_lpt_sources", "peaks"};
 
 struct EvPair { int kind; hipEvent_t a, b; double bytes; };
 
@@ -1921,6 +1921,127 @@ extern "C" int pf_select_sorted(pf_ctx *c, float flast, size_t capacity, unsigne
   HIPCHK(c, hipStreamSynchronize(c->stream));
   hipFree(d_idx);
   return 0;
+}
+
+// ---- count_peaks on the device (pf_peaks.hip) ----
+static int peak_region(int task, const char *who, int n, const pf_peak_region *rg, PfPeakParams *p) {
+  int d = 0;
+  const int why = pf_peak_region_setup(n, rg, p, &d);
+  if (why == 1) return pf_fail(task, "%s: region does not fit the box: len[%d] = %d outside [1, %d]", who, d, rg->len[d], n);
+  if (why) return pf_fail(task, "%s: region does not fit the box: safe[%d] = %d, 2 * safe > len[%d] = %d (or negative)", who, d, rg->safe[d], d, rg->len[d]);
+  return 0;
+}
+// The x-neighbours of the slab's first and last plane.  One rank: the slab's own last and first plane, in place.  Slabs: every rank
+// sends its first and its last plane to the two neighbours of the rank ring through the block all-to-all (a block of two planes
+// per peer; the blocks of the other peers travel as they are and are not looked at), once per call.  *scratch: to hipFree after the kernel
+static int peak_halo(pf_ctx *c, PfPeakParams *p, void **scratch) {
+  const size_t plane = (size_t)c->n * c->n * (size_t)c->pb;
+  const char *slab = (const char *)c->fmax;
+  *scratch = nullptr;
+  if (c->P == 1) {
+    p->halo_lo = slab + (size_t)(c->nxl - 1) * plane; p->halo_hi = slab;
+    return 0;
+  }
+  if (!c->a2a) return pf_fail(c->rank, "no exchange installed for %d ranks (pf_set_exchange / pf_init_rccl)", c->P);
+  const size_t block = 2 * plane, half = (size_t)c->P * block;
+  char *buf = nullptr;
+  HIPCHK(c, hipMalloc((void **)&buf, 2 * half));
+  *scratch = buf;
+  char *send = buf, *recv = buf + half;
+  HIPCHK(c, hipMemsetAsync(send, 0, half, c->stream));
+  const int left = (c->rank + c->P - 1) % c->P, right = (c->rank + 1) % c->P;
+  for (int q : {left, right}) {
+    HIPCHK(c, hipMemcpyAsync(send + (size_t)q * block, slab, plane, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(send + (size_t)q * block + plane, slab + (size_t)(c->nxl - 1) * plane, plane, hipMemcpyDeviceToDevice, c->stream));
+  }
+  {
+    KTimer t(c, KS_EXCHANGE, (double)half);
+    if (c->a2a(c->a2a_user, send, recv, block, (void *)c->stream)) return pf_fail(c->rank, "all-to-all failed");
+  }
+  p->halo_lo = recv + (size_t)left * block + plane;  // the last plane of the rank before
+  p->halo_hi = recv + (size_t)right * block;         // the first plane of the rank after
+  return 0;
+}
+static int peak_params(pf_ctx *c, const char *who, double flast, const pf_peak_region *region, PfPeakParams *p, void **scratch) {
+  *scratch = nullptr;
+  if (!c->products_init) return pf_fail(c->rank, "%s: products not computed", who);
+  memset(p, 0, sizeof(*p));
+  if (peak_region(c->rank, who, c->n, region, p)) return 1;
+  p->fmax = c->fmax; p->n = c->n; p->nxl = c->nxl; p->x0 = c->rank * c->nxl; p->flast = flast;
+  p->counters = c->hist;  // (PF_NBINS counters that pf_fmax_pdf clears before it uses them)
+  HIPCHK(c, hipMemsetAsync(c->hist, 0, 3 * sizeof(unsigned long long), c->stream));
+  return peak_halo(c, p, scratch);
+}
+
+extern "C" int pf_count_peaks(pf_ctx *c, double flast, const pf_peak_region *region, unsigned long long peaks[2]) {
+  if (!c || !peaks) return pf_fail(0, "pf_count_peaks: null argument");
+  PfPeakParams p;
+  void *scratch = nullptr;
+  if (peak_params(c, "pf_count_peaks", flast, region, &p, &scratch)) { hipStreamSynchronize(c->stream); hipFree(scratch); return 1; }
+  int rc;
+  {
+    KTimer t(c, KS_PEAKS, (double)ncell(c) * c->pb);
+    rc = pf_launch_peaks(c->pb, p, c->stream);
+  }
+  if (rc) { hipStreamSynchronize(c->stream); hipFree(scratch); return pf_fail(c->rank, "pf_count_peaks: launch failed"); }
+  rc = allreduce_dev(c, c->hist, 2, 1);
+  if (!rc && hipMemcpyAsync(peaks, c->hist, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = 1;
+  if (hipStreamSynchronize(c->stream) != hipSuccess) rc = 1;
+  hipFree(scratch);
+  return rc ? pf_fail(c->rank, "pf_count_peaks: reduction or copy failed") : 0;
+}
+
+extern "C" int pf_select_peaks(pf_ctx *c, double flast, size_t capacity, unsigned int *cell_index, float *fmax, size_t *count) {
+  if (!c || !count) return pf_fail(0, "pf_select_peaks: null argument");
+  if (c->pb != 4) return pf_fail(c->rank, "pf_select_peaks: fp32 Fmax only (not with PF_FLAG_DOUBLE_PRODUCTS)");
+  if (ncell(c) > 0xFFFFFFFFull) return pf_fail(c->rank, "pf_select_peaks: more than 2^32 cells on one rank");
+  PfPeakParams p;
+  void *scratch = nullptr;
+  unsigned long long h[2] = {0, 0};
+  unsigned int *d_idx = nullptr; float *d_f = nullptr;
+  int rc = peak_params(c, "pf_select_peaks", flast, nullptr, &p, &scratch);
+  if (rc) { hipStreamSynchronize(c->stream); hipFree(scratch); return 1; }
+  // count pass (sizes the key buffer), then the same kernel appending keys
+  {
+    KTimer t(c, KS_PEAKS, (double)ncell(c) * c->pb);
+    rc = pf_launch_peaks(c->pb, p, c->stream);
+  }
+  if (!rc && hipMemcpyAsync(h, c->hist, sizeof(h), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = 1;
+  if (hipStreamSynchronize(c->stream) != hipSuccess) rc = 1;
+  if (!rc && h[0]) {
+    KTimer t(c, KS_PEAKS, (double)ncell(c) * c->pb + 8.0 * (double)h[0]);
+    rc = pf_select_peaks_device(p, (size_t)h[0], &d_idx, &d_f, c->stream);
+  }
+  hipFree(scratch);
+  if (rc) return pf_fail(c->rank, "pf_select_peaks: device pass failed (out of memory?)");
+  *count = (size_t)h[0];
+  const size_t m = *count < capacity ? *count : capacity;
+  if (m && cell_index) HIPCHK(c, hipMemcpyAsync(cell_index, d_idx, m * sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+  if (m && fmax) HIPCHK(c, hipMemcpyAsync(fmax, d_f, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  hipFree(d_idx);
+  return 0;
+}
+
+// context-free tap: the kernel on a caller's n^3 fp32 field (one rank: the x-halo is the field's own last and first plane)
+extern "C" int pf_debug_peaks(int n, const float *fmax_host, double flast, const pf_peak_region *region, unsigned long long peaks[2]) {
+  if (!fmax_host || !peaks || n < 1 || n > 2048) return pf_fail(0, "pf_debug_peaks: bad argument");
+  PfPeakParams p;
+  memset(&p, 0, sizeof(p));
+  if (peak_region(0, "pf_debug_peaks", n, region, &p)) return 1;
+  const size_t nc = (size_t)n * n * n;
+  float *d = nullptr;
+  unsigned long long *cnt = nullptr;
+  int rc = 1;
+  if (hipMalloc((void **)&d, nc * sizeof(float)) == hipSuccess && hipMalloc((void **)&cnt, 3 * sizeof(unsigned long long)) == hipSuccess &&
+      hipMemcpy(d, fmax_host, nc * sizeof(float), hipMemcpyHostToDevice) == hipSuccess && hipMemset(cnt, 0, 3 * sizeof(unsigned long long)) == hipSuccess) {
+    p.fmax = d; p.halo_lo = d + (size_t)(n - 1) * n * n; p.halo_hi = d;
+    p.n = n; p.nxl = n; p.x0 = 0; p.flast = flast; p.counters = cnt;
+    if (!pf_launch_peaks(4, p, nullptr) && hipDeviceSynchronize() == hipSuccess &&
+        hipMemcpy(peaks, cnt, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+  }
+  hipFree(d); hipFree(cnt);
+  return rc ? pf_fail(0, "pf_debug_peaks: device pass failed") : 0;
 }
 
 // per-particle payload of one block of the timeless snapshot (src/write_snapshot.c:207-342, 620-855)

@@ -224,6 +224,21 @@ void pf_gfft_destroy(void *plan);
 int pf_launch_debug_math(int which, const double *a, const double *b, size_t count, double *out, hipStream_t st);
 // pf_select_sort.hip
 int pf_select_sort_device(const float *fmax, size_t ncell, float flast, unsigned int **d_idx, float **d_f, size_t *count, hipStream_t st);
+int pf_sort_keys_device(unsigned long long *keys_in, size_t count, unsigned int **d_idx, float **d_f, hipStream_t st);  // takes keys_in over
+// pf_peaks.hip: count_peaks (src/fragment.c:605-706) on a slab
+struct PfPeakParams {
+  const void *fmax;               // this rank's slab [nxl][n][n] of PRODFLOAT
+  const void *halo_lo, *halo_hi;  // the planes x - 1 of the first and x + 1 of the last local plane, [n][n]
+  int n, nxl, x0;                 // x0: global x of the first local plane
+  double flast;
+  int start[3], lo[3], hi[3], glo[3], ghi[3];  // pf_peak_region_setup: examined and well resolved ranges in the region's own coordinates
+  unsigned long long *counters;   // device: [0] peaks, [1] well resolved peaks, [2] key cursor
+  unsigned long long *keys;       // null: count only
+  size_t key_cap;
+};
+int pf_peak_region_setup(int n, const pf_peak_region *rg, PfPeakParams *p, int *bad);
+int pf_launch_peaks(int pb, const PfPeakParams &p, hipStream_t st);
+int pf_select_peaks_device(PfPeakParams p, size_t npeaks, unsigned int **d_idx, float **d_f, hipStream_t st);
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);

@@ -16,19 +16,9 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "pf_internal.h"
+#include "pf_keys.h"
 
 #define PF_SEL_BLOCK 256
-
-__device__ __forceinline__ unsigned int pf_desc_key(float f) {
-  unsigned int u = __float_as_uint(f);
-  u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;  // ascending-orderable
-  return ~u;                                   // descending
-}
-__device__ __forceinline__ float pf_key_to_float(unsigned int k) {
-  unsigned int u = ~k;
-  u ^= (u >> 31) ? 0x80000000u : 0xFFFFFFFFu;
-  return __uint_as_float(u);
-}
 
 __global__ void __launch_bounds__(PF_SEL_BLOCK) k_count_selected(const float *__restrict__ fmax, size_t ncell, float flast, unsigned long long *count) {
   unsigned long long mine = 0;
@@ -74,12 +64,35 @@ static int sel_grid(size_t n) {
 
 #define SELCHK(x) do { if ((x) != hipSuccess) { rc = 1; goto done; } } while (0)
 
+// h keys in keys_in (hipMalloc'ed; this function takes it over) -> the cells in key order.  device arrays out: *d_idx / *d_f (ONE
+// allocation, the caller frees *d_idx).  Shared by pf_select_sorted and pf_select_peaks (pf_peaks.hip)
+int pf_sort_keys_device(unsigned long long *keys_in, size_t h, unsigned int **d_idx, float **d_f, hipStream_t st) {
+  int rc = 0;
+  unsigned long long *keys_out = nullptr;
+  void *tmp = nullptr;
+  size_t tmp_bytes = 0;
+  *d_idx = nullptr; *d_f = nullptr;
+  SELCHK(hipMalloc(&keys_out, h * sizeof(unsigned long long)));
+  SELCHK(rocprim::radix_sort_keys(nullptr, tmp_bytes, keys_in, keys_out, h, 0, 64, st));
+  SELCHK(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 8));
+  SELCHK(rocprim::radix_sort_keys(tmp, tmp_bytes, keys_in, keys_out, h, 0, 64, st));
+  // keys_in is dead: the two output arrays fit in it (8 bytes per entry)
+  *d_idx = (unsigned int *)keys_in;
+  *d_f = (float *)((unsigned int *)keys_in + h);
+  hipLaunchKernelGGL(k_unpack_keys, dim3(sel_grid(h)), dim3(PF_SEL_BLOCK), 0, st, keys_out, h, *d_idx, *d_f);
+  SELCHK(hipGetLastError());
+  SELCHK(hipStreamSynchronize(st));
+  keys_in = nullptr;  // now owned by the caller through *d_idx
+done:
+  hipFree(keys_in); hipFree(keys_out); hipFree(tmp);
+  if (rc) { *d_idx = nullptr; *d_f = nullptr; }
+  return rc;
+}
+
 // device arrays out: *d_idx / *d_f (hipMalloc'ed here, the caller frees), *count
 int pf_select_sort_device(const float *fmax, size_t ncell, float flast, unsigned int **d_idx, float **d_f, size_t *count, hipStream_t st) {
   int rc = 0;
-  unsigned long long *d_count = nullptr, *keys_in = nullptr, *keys_out = nullptr;
-  void *tmp = nullptr;
-  size_t tmp_bytes = 0;
+  unsigned long long *d_count = nullptr, *keys_in = nullptr;
   unsigned long long h = 0;
   *d_idx = nullptr; *d_f = nullptr; *count = 0;
   SELCHK(hipMalloc(&d_count, 2 * sizeof(unsigned long long)));
@@ -90,22 +103,12 @@ int pf_select_sort_device(const float *fmax, size_t ncell, float flast, unsigned
   *count = (size_t)h;
   if (h) {
     SELCHK(hipMalloc(&keys_in, h * sizeof(unsigned long long)));
-    SELCHK(hipMalloc(&keys_out, h * sizeof(unsigned long long)));
     hipLaunchKernelGGL(k_select_keys, dim3(sel_grid(ncell)), dim3(PF_SEL_BLOCK), 0, st, fmax, ncell, flast, keys_in, d_count + 1);
-    SELCHK(rocprim::radix_sort_keys(nullptr, tmp_bytes, keys_in, keys_out, (size_t)h, 0, 64, st));
-    SELCHK(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 8));
-    SELCHK(rocprim::radix_sort_keys(tmp, tmp_bytes, keys_in, keys_out, (size_t)h, 0, 64, st));
-    // keys_in is dead: the two output arrays fit in it (8 bytes per entry)
-    *d_idx = (unsigned int *)keys_in;
-    *d_f = (float *)((unsigned int *)keys_in + h);
-    hipLaunchKernelGGL(k_unpack_keys, dim3(sel_grid(h)), dim3(PF_SEL_BLOCK), 0, st, keys_out, (size_t)h, *d_idx, *d_f);
-    SELCHK(hipGetLastError());
-    SELCHK(hipStreamSynchronize(st));
-    keys_in = nullptr;  // now owned by the caller through *d_idx
+    rc = pf_sort_keys_device(keys_in, (size_t)h, d_idx, d_f, st);
+    keys_in = nullptr;  // taken over by the sort
   }
 done:
-  hipFree(d_count); hipFree(keys_in); hipFree(keys_out); hipFree(tmp);
-  if (rc) { hipFree(*d_idx); *d_idx = nullptr; *d_f = nullptr; }
+  hipFree(d_count); hipFree(keys_in);
   return rc;
 }
 
