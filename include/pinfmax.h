@@ -327,6 +327,31 @@ int pf_count_peaks(pf_ctx *ctx, double flast, const pf_peak_region *region, unsi
 int pf_select_peaks(pf_ctx *ctx, double flast, size_t capacity, unsigned int *cell_index, float *fmax, size_t *count);
 /* test tap without a context: the same kernel on a caller's n^3 fp32 field (host, index z + n*(y + n*x)) */
 int pf_debug_peaks(int n, const float *fmax_host, double flast, const pf_peak_region *region, unsigned long long peaks[2]);
+/* The step between the two on the device: distribute() (src/distribute.c:58-175), which moves the product records from the FFT
+   slabs to the fragmentation sub-boxes.  pf_distribute gives THIS RANK'S CONTRIBUTION TO ONE TARGET SUB-BOX: what keep_data()
+   (:547-600) stores when the target is the rank itself and what send_data() (:300-416) puts on the wire otherwise.
+   sub = subbox.stabl (may be negative; any start is reduced to the periodic box) and subbox.Lgwbl of the TARGET.
+   Region and order: the cells of intersection(my_fft_box, sub) (:178-297; the x-slab spans y and z) -- up to eight boxes when the
+   sub-box wraps, in the order intersection() emits them, and within a box by ascending i of INDEX_TO_COORD(i, ., ., ., box + 3)
+   (src/pinocchio.h:84, z fastest).
+   Selection: a cell is taken when the bit subbox_space_index(i, box) (:627-645) of `map` is set (host; UINTLEN = 32 bits per
+   word, bit p % 32 of word p / 32, prod(len) bits: frag_map_update / frag_map through build_distmap, :670-682; NULL = every bit
+   set) and (double)Fmax >= flast (update_distmap, :685-698).  NaN is never taken.
+   Output: every taken cell appends one record in the caller's layout to `frag` -- the conventions of pf_get_products; bytes no
+   non-negative offset names are zero (the *_prev fields of a RECOMPUTE_DISPLACEMENTS build among them); stride and offsets are
+   multiples of four -- and its sub-box-space index to `frag_pos`.  *count receives the number taken; the first
+   min(*count, capacity) entries are copied, counting goes on beyond capacity as frag_offset does (:586-592).  frag and frag_pos
+   may each be NULL (both: a count-only call).  A sub-box that misses the slab gives *count = 0.
+   Needs the products of a sweep.  NOT collective and nothing goes through the exchange callbacks: the caller owns the transport
+   that carries a contribution to the sub-box's owner, and concatenates the contributions in distribute()'s order -- its own
+   first, then those of the hypercube loop (:109-148) -- to get the reference's frag[] / frag_pos[].  INTEGRATION.md has the loop. */
+typedef struct { int start[3], len[3]; } pf_subbox;
+int pf_distribute(pf_ctx *ctx, double flast, const pf_subbox *sub, const unsigned int *map, const pf_product_layout *layout,
+                  size_t capacity, void *frag, unsigned int *frag_pos, size_t *count);
+/* test tap without a context: the selection and ordering kernels on a caller's slab of an fp32 field -- planes x0 .. x0 + nxl - 1
+   of an n^3 box, host, index z + n*(y + n*x_local); returns frag_pos and the local cell index of each taken cell */
+int pf_debug_distribute(int n, int x0, int nxl, const float *fmax_host, double flast, const pf_subbox *sub, const unsigned int *map,
+                        size_t capacity, unsigned int *frag_pos, unsigned int *cell_index, size_t *count);
 /* Per-particle payload of one block of the "timeless snapshot" (write_timeless_snapshot, src/write_snapshot.c:207-342)
    for this rank's slab, from the SoA columns in HBM: name = "ID  " (1 + global index as MYIDTYPE of id_bytes = 4 or 8,
    :648-664), "FMAX" float, "RMAX" int, "ZEL " / "2LPT" / "31PT" / "32PT" float[3] per particle (:700-855). */

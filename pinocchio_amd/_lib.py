@@ -45,6 +45,10 @@ class PeakRegion(C.Structure):
     _fields_ = [("start", C.c_int * 3), ("len", C.c_int * 3), ("safe", C.c_int * 3)]
 
 
+class SubBox(C.Structure):
+    _fields_ = [("start", C.c_int * 3), ("len", C.c_int * 3)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -97,6 +101,10 @@ PROTOTYPES = {
     "pf_count_peaks": (C.c_int, [_vp, C.c_double, C.POINTER(PeakRegion), C.POINTER(C.c_ulonglong)]),
     "pf_select_peaks": (C.c_int, [_vp, C.c_double, C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_float), C.POINTER(C.c_size_t)]),
     "pf_debug_peaks": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_double, C.POINTER(PeakRegion), C.POINTER(C.c_ulonglong)]),
+    "pf_distribute": (C.c_int, [_vp, C.c_double, C.POINTER(SubBox), C.POINTER(C.c_uint), C.POINTER(ProductLayout), C.c_size_t, _vp,
+                                C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]),
+    "pf_debug_distribute": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_double, C.POINTER(SubBox), C.POINTER(C.c_uint),
+                                      C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]),
     "pf_set_collapse_model": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "pf_set_modified_gravity": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "pf_set_tabulated_ct": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),

@@ -63,6 +63,50 @@ def debug_peaks(fmax: np.ndarray, flast: float, region=None):
     return int(out[0]), int(out[1])
 
 
+def _subbox(start, length):
+    return _lib.SubBox((C.c_int * 3)(*map(int, start)), (C.c_int * 3)(*map(int, length)))
+
+
+def _distmap(bits, length):
+    """frag_map / frag_map_update of the target sub-box: uint32 words, bit p % 32 of word p // 32 for sub-box-space index p"""
+    if bits is None:
+        return None, None
+    m = np.ascontiguousarray(bits, dtype=np.uint32).ravel()
+    cells = int(length[0]) * int(length[1]) * int(length[2])
+    if m.size * 32 < cells:
+        raise ValueError(f"map of {m.size} words for a sub-box of {cells} cells")
+    return m, m.ctypes.data_as(C.POINTER(C.c_uint))
+
+
+def debug_distribute(fmax_slab: np.ndarray, x0: int, flast: float, start, length, map=None, capacity=None):
+    """distribute()'s selection and order (src/distribute.c:547-698) by the device kernels on a caller's slab [nxl][n][n] of an fp32
+    field, planes x0 .. x0 + nxl - 1 of the n^3 box -> (frag_pos, local cell index, count); capacity None: room for all"""
+    L = _lib.load()
+    f = np.ascontiguousarray(fmax_slab, dtype=np.float32)
+    nxl, n = f.shape[0], f.shape[1]
+    if f.shape != (nxl, n, n):
+        raise ValueError(f"slab shape {f.shape}")
+    sub = _subbox(start, length)
+    keep, mp = _distmap(map, length)
+    cnt = C.c_size_t()
+    fp = f.ctypes.data_as(C.POINTER(C.c_float))
+
+    def call(cap, pos, idx):
+        if L.pf_debug_distribute(n, int(x0), nxl, fp, float(flast), C.byref(sub), mp, cap,
+                                 pos.ctypes.data_as(C.POINTER(C.c_uint)) if pos is not None else None,
+                                 idx.ctypes.data_as(C.POINTER(C.c_uint)) if idx is not None else None, C.byref(cnt)):
+            raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_distribute failed")
+
+    if capacity is None:
+        call(0, None, None)          # a count-only call sizes the arrays
+        capacity = cnt.value
+    pos = np.empty(int(capacity), dtype=np.uint32)
+    idx = np.empty(int(capacity), dtype=np.uint32)
+    call(int(capacity), pos, idx)
+    m = min(cnt.value, int(capacity))
+    return pos[:m], idx[:m], int(cnt.value)
+
+
 class Fmax:
     """One rank's context: an x-slab of an n^3 grid on one MI355X."""
 
@@ -282,6 +326,43 @@ class Fmax:
         self._chk(self.L.pf_select_peaks(self.h, float(flast), cnt.value, idx.ctypes.data_as(C.POINTER(C.c_uint)),
                                          f.ctypes.data_as(C.POINTER(C.c_float)), C.byref(cnt)))
         return idx, f
+
+    def product_layout(self):
+        """(pf_product_layout, numpy dtype) of the record products() returns"""
+        lay = _lib.ProductLayout()
+        self.L.pf_layout_3lpt(C.byref(lay))
+        if not self.double_products:
+            return lay, PRODUCT_DTYPE
+        lay.stride, lay.off_Rmax, lay.off_Fmax = 112, 0, 8
+        lay.off_Vel, lay.off_Vel_2LPT, lay.off_Vel_3LPT_1, lay.off_Vel_3LPT_2 = 16, 40, 64, 88
+        return lay, PRODUCT_DTYPE_DP
+
+    def distribute(self, flast: float, start, length, map=None, layout=None, capacity=None):
+        """This rank's contribution to the sub-box (start[3], length[3]) = (subbox.stabl, subbox.Lgwbl) in distribute()
+        (src/distribute.c:58-175): the cells of intersection(this slab, sub-box) whose bit of `map` (uint32 words, None: every
+        bit) is set and whose Fmax >= flast, in the reference's order -> (records, frag_pos, count).  layout None: the record of
+        products() as a structured array; a _lib.ProductLayout: rows of `stride` bytes.  capacity None: room for all (a
+        count-only call first); otherwise at most `capacity` entries are returned and count still says how many were taken.
+        Not collective."""
+        sub = _subbox(start, length)
+        keep, mp = _distmap(map, length)
+        dtype = None
+        if layout is None:
+            layout, dtype = self.product_layout()
+        cnt = C.c_size_t()
+        if capacity is None:
+            self._chk(self.L.pf_distribute(self.h, float(flast), C.byref(sub), mp, C.byref(layout), 0, None, None, C.byref(cnt)))
+            capacity = cnt.value
+        capacity = int(capacity)
+        rec = np.zeros((capacity, layout.stride), dtype=np.uint8)
+        pos = np.empty(capacity, dtype=np.uint32)
+        self._chk(self.L.pf_distribute(self.h, float(flast), C.byref(sub), mp, C.byref(layout), capacity, rec.ctypes.data_as(C.c_void_p),
+                                       pos.ctypes.data_as(C.POINTER(C.c_uint)), C.byref(cnt)))
+        m = min(cnt.value, capacity)
+        rec = rec[:m]
+        if dtype is not None:
+            rec = rec.view(dtype).reshape(m)
+        return rec, pos[:m], int(cnt.value)
 
     def block(self, name: str, id_bytes: int = 4) -> np.ndarray:
         """one block of the timeless snapshot (src/write_snapshot.c:207-342) for this rank's slab"""

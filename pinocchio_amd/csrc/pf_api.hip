@@ -69,13 +69,13 @@ extern "C" const char *pf_last_error(void) { return g_err; }
 enum {
   KS_XPASS_HESS = 0, KS_YPASS_HESS, KS_ZPASS_HESS, KS_COLLAPSE, KS_LPT_SRC, KS_LPT_ACC, KS_R2C_Z, KS_YPASS_FWD,
   KS_XPASS_FWD, KS_XPASS_DISP, KS_YPASS_DISP, KS_ZPASS_DISP, KS_XPASS_PLAIN, KS_YPASS_PLAIN, KS_ZPASS_PLAIN,
-  KS_EXCHANGE, KS_MISC, KS_ZCOLLAPSE, KS_ZPASS_INV, KS_COLLAPSE_INV, KS_ZPASS_LPT3B, KS_COLLAPSE_SRC, KS_PEAKS, KS_COUNT
+  KS_EXCHANGE, KS_MISC, KS_ZCOLLAPSE, KS_ZPASS_INV, KS_COLLAPSE_INV, KS_ZPASS_LPT3B, KS_COLLAPSE_SRC, KS_PEAKS, KS_DISTRIBUTE, KS_COUNT
 };
 static const char *ks_names[KS_COUNT] = {
     "xpass_hess_1to3", "ypass_hess_3to6", "zpass_c2r_hess_6", "collapse", "lpt_sources", "lpt_accum", "zpass_r2c",
     "ypass_fwd", "xpass_fwd", "xpass_disp_1to2", "ypass_disp_2to3", "zpass_c2r_disp_3", "xpass_plain", "ypass_plain",
     "zpass_c2r_plain", "exchange", "misc", "zpass_collapse_fused", "zpass_c2r_hess_6to3inv", "collapse_inv", "zpass_c2r_hess_6_lpt3b",
-    "collapse_lpt_sources", "peaks"};
+    "collapse_lpt_sources", "peaks", "distribute"};
 
 struct EvPair { int kind; hipEvent_t a, b; double bytes; };
 
@@ -338,6 +338,7 @@ static void read_tuning(PfTuning *t) {
   if (t->handoff_chunk_mb <= 0) t->handoff_chunk_mb = 256;
   t->handoff_threads = env_int("PF_HANDOFF_THREADS", 0);
   t->host_register = env_int("PF_HOST_REGISTER", 0) != 0;
+  t->distribute_lds = env_int("PF_DISTRIBUTE_LDS", 1) != 0;
   // fault injection for the tests of the exchange pipeline (tests/test_gpu_multirank.py): "recv" drops the wait of the
   // compute stream for the exchange it is about to consume, "send" the wait of the exchange for the x-pass that fills its blocks
   const char *fault = getenv("PF_DEBUG_PIPELINE_FAULT");
@@ -2044,6 +2045,122 @@ extern "C" int pf_debug_peaks(int n, const float *fmax_host, double flast, const
   return rc ? pf_fail(0, "pf_debug_peaks: device pass failed") : 0;
 }
 
+// ---- distribute() for one target sub-box (pf_distribute.hip) ----
+static int dist_table(int task, const char *who, int n, int x0, int nxl, const pf_subbox *sub, PfDistTable *t) {
+  int d = 0;
+  const int why = pf_dist_table(n, x0, nxl, sub, t, &d);
+  if (why == 1) return pf_fail(task, "%s: sub-box does not fit the box: len[%d] = %d outside [1, %d]", who, d, sub->len[d], n);
+  if (why) return pf_fail(task, "%s: a sub-box of more than 2^32 cells (frag_pos is 32-bit)", who);
+  return 0;
+}
+struct DistGuard { PfDistScratch *s; ~DistGuard() { pf_dist_release(s); } };
+
+// This rank's contribution to one sub-box.  Flag pass and scan on the compute stream, one 8-byte read-back for the count; then the
+// records leave through the hand-off machinery of pf_get_products: piece k is packed into one of the two staging fields (records,
+// then their frag_pos) and copied into its pinned buffer while the host threads move piece k - 1 into the caller's arrays.
+extern "C" int pf_distribute(pf_ctx *c, double flast, const pf_subbox *sub, const unsigned int *map, const pf_product_layout *l,
+                             size_t capacity, void *frag, unsigned int *frag_pos, size_t *count) {
+  if (!c || !sub || !count || (frag && !l)) return pf_fail(c ? c->rank : 0, "pf_distribute: null argument");
+  if (!c->products_init) return pf_fail(c->rank, "pf_distribute: products not computed");
+  PfDistTable t;
+  if (dist_table(c->rank, "pf_distribute", c->n, c->rank * c->nxl, c->nxl, sub, &t)) return 1;
+  PfDistRecord rec;
+  memset(&rec, 0, sizeof(rec));
+  size_t stride = 0;
+  if (frag) {
+    const int why = pf_dist_record(c->pb, l, &rec);
+    if (why == 1) return pf_fail(c->rank, "pf_distribute: bad layout: stride %zu and the offsets must be multiples of four, fields inside the record", l->stride);
+    if (why) return pf_fail(c->rank, "pf_distribute: fields of the layout overlap");
+    stride = l->stride;
+    if (l->off_Vel >= 0 || l->off_Vel_2LPT >= 0 || l->off_Vel_3LPT_1 >= 0 || l->off_Vel_3LPT_2 >= 0) PFCHK(c, velocities_ready(c));
+  }
+  PhaseTimer pt(c, 3);
+  PfDistScratch s;
+  memset(&s, 0, sizeof(s));
+  DistGuard guard{&s};
+  unsigned long long total = 0;
+  const double cells = 64.0 * (double)t.wave0[t.nbox];
+  {
+    KTimer kt(c, KS_DISTRIBUTE, cells * (c->pb + 0.125 + (map ? 0.125 : 0.0)));
+    if (pf_dist_select(t, c->pb, c->fmax, flast, map, &s, c->stream, &total)) return pf_fail(c->rank, "pf_distribute: selection failed (out of memory?)");
+  }
+  *count = (size_t)total;
+  const size_t m = *count < capacity ? *count : capacity;
+  if (!m || (!frag && !frag_pos)) return 0;
+  PfHandoff *h;
+  if (handoff_get(c, &h)) return 1;
+  PFCHK(c, handoff_begin(c, h));
+  const size_t per = h->chunk / (stride + (frag_pos ? 4 : 0));
+  if (!per) return pf_fail(c->rank, "pf_distribute: a record of %zu bytes does not fit the staging pieces", stride);
+  const size_t np = (m + per - 1) / per;
+  const bool lds = c->tune.distribute_lds && rec.nwords <= PF_DIST_MAX_WORDS;
+  auto issue = [&](size_t k) -> int {
+    const int b = (int)(k & 1);
+    const size_t first = k * per, cnt = m - first < per ? m - first : per;
+    char *stage = handoff_dev(c, b);
+    unsigned int *pos_dev = (unsigned int *)(stage + per * stride);
+    {
+      KTimer kt(c, KS_DISTRIBUTE, (double)t.ngroups * PF_DIST_GROUP_WAVES * 8.0 + (double)cnt * (2.0 * stride + (frag_pos ? 4.0 : 0.0)), h->st[b]);
+      if (frag && !lds) HIPCHK(c, hipMemsetAsync(stage, 0, cnt * stride, h->st[b]));   // (the plain pack writes the named words only)
+      PFCHK(c, pf_dist_pack(t, s, c->pb, c->fmax, c->rmax, c->vel12, ncell(c), rec, stride, first, cnt, frag ? stage : nullptr,
+                            frag_pos ? pos_dev : nullptr, nullptr, lds, h->st[b]));
+    }
+    if (frag) HIPCHK(c, hipMemcpyAsync(h->pin[b], stage, cnt * stride, hipMemcpyDeviceToHost, h->st[b]));
+    if (frag_pos) HIPCHK(c, hipMemcpyAsync(h->pin[b] + per * stride, pos_dev, cnt * sizeof(unsigned int), hipMemcpyDeviceToHost, h->st[b]));
+    return 0;
+  };
+  if (issue(0)) return 1;
+  for (size_t k = 0; k < np; k++) {
+    if (k + 1 < np && issue(k + 1)) return 1;
+    const int b = (int)(k & 1);
+    HIPCHK(c, hipStreamSynchronize(h->st[b]));
+    const size_t first = k * per, cnt = m - first < per ? m - first : per;
+    if (frag) {
+      char *dst = (char *)frag + first * stride; const char *src = h->pin[b];
+      h->pool->run(cnt * stride, [=](size_t a, size_t e) { memcpy(dst + a, src + a, e - a); });
+    }
+    if (frag_pos) {
+      char *dst = (char *)(frag_pos + first); const char *src = h->pin[b] + per * stride;
+      h->pool->run(cnt * sizeof(unsigned int), [=](size_t a, size_t e) { memcpy(dst + a, src + a, e - a); });
+    }
+  }
+  return 0;
+}
+
+// context-free tap: flag pass, scan and the ordering part of the pack pass on a caller's slab of an fp32 field
+extern "C" int pf_debug_distribute(int n, int x0, int nxl, const float *fmax_host, double flast, const pf_subbox *sub, const unsigned int *map,
+                                   size_t capacity, unsigned int *frag_pos, unsigned int *cell_index, size_t *count) {
+  if (!fmax_host || !sub || !count || n < 1 || n > 2048 || nxl < 1 || x0 < 0 || x0 + nxl > n) return pf_fail(0, "pf_debug_distribute: bad argument");
+  const size_t nc = (size_t)nxl * n * n;
+  if (nc > 0xFFFFFFFFull) return pf_fail(0, "pf_debug_distribute: more than 2^32 cells in the slab");
+  PfDistTable t;
+  if (dist_table(0, "pf_debug_distribute", n, x0, nxl, sub, &t)) return 1;
+  PfDistScratch s;
+  memset(&s, 0, sizeof(s));
+  DistGuard guard{&s};
+  PfDistRecord rec;
+  memset(&rec, 0, sizeof(rec));
+  float *d = nullptr;
+  unsigned int *out = nullptr;
+  unsigned long long total = 0;
+  int rc = 1;
+  if (hipMalloc((void **)&d, nc * sizeof(float)) == hipSuccess && hipMemcpy(d, fmax_host, nc * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+      !pf_dist_select(t, 4, d, flast, map, &s, nullptr, &total)) {
+    *count = (size_t)total;
+    const size_t m = *count < capacity ? *count : capacity;
+    rc = 0;
+    if (m && (frag_pos || cell_index)) {
+      rc = 1;
+      if (hipMalloc((void **)&out, 2 * m * sizeof(unsigned int)) == hipSuccess &&
+          !pf_dist_pack(t, s, 4, d, nullptr, nullptr, nc, rec, 0, 0, m, nullptr, out, out + m, false, nullptr) && hipDeviceSynchronize() == hipSuccess &&
+          (!frag_pos || hipMemcpy(frag_pos, out, m * sizeof(unsigned int), hipMemcpyDeviceToHost) == hipSuccess) &&
+          (!cell_index || hipMemcpy(cell_index, out + m, m * sizeof(unsigned int), hipMemcpyDeviceToHost) == hipSuccess)) rc = 0;
+    }
+  }
+  hipFree(d); hipFree(out);
+  return rc ? pf_fail(0, "pf_debug_distribute: device pass failed") : 0;
+}
+
 // per-particle payload of one block of the timeless snapshot (src/write_snapshot.c:207-342, 620-855)
 extern "C" int pf_get_block(pf_ctx *c, const char *name, int id_bytes, void *host) {
   if (!c || !name || !host) return pf_fail(0, "pf_get_block: null argument");
@@ -2230,7 +2347,7 @@ extern "C" int pf_get_cputime(pf_ctx *c, pf_cputime *t) {
   resolve_events(c);
   double fft = 0;
   for (int k = 0; k < KS_COUNT; k++)
-    if (k != KS_COLLAPSE && k != KS_COLLAPSE_INV && k != KS_COLLAPSE_SRC && k != KS_LPT_SRC && k != KS_LPT_ACC && k != KS_MISC) fft += 1e-3 * c->ks_ms[k];
+    if (k != KS_COLLAPSE && k != KS_COLLAPSE_INV && k != KS_COLLAPSE_SRC && k != KS_LPT_SRC && k != KS_LPT_ACC && k != KS_MISC && k != KS_DISTRIBUTE) fft += 1e-3 * c->ks_ms[k];
   t->fft = fft;
   return 0;
 }

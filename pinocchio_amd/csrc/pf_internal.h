@@ -25,6 +25,7 @@ struct PfTuning {
   int handoff_chunk_mb, handoff_threads;  // PF_HANDOFF_CHUNK_MB, PF_HANDOFF_THREADS: pieces and host threads of the hand-off (pf_api.hip PfHandoff)
   bool host_register;       // PF_HOST_REGISTER: register the caller's product array with the driver, DMA straight into it
   bool preflight;           // PF_PREFLIGHT: pf_create holds the plan's bytes against the device's free memory before it allocates
+  bool distribute_lds;      // PF_DISTRIBUTE_LDS: pf_distribute stages the records of a round in LDS (1, default) or writes one lane per record (0)
   bool gtab;                // PF_GTAB: the inverse growing mode of the fast flavour from the polynomial table (pf_gtab.h)
 };
 
@@ -239,6 +240,32 @@ struct PfPeakParams {
 int pf_peak_region_setup(int n, const pf_peak_region *rg, PfPeakParams *p, int *bad);
 int pf_launch_peaks(int pb, const PfPeakParams &p, hipStream_t st);
 int pf_select_peaks_device(PfPeakParams p, size_t npeaks, unsigned int **d_idx, float **d_f, hipStream_t st);
+// pf_distribute.hip: distribute() (src/distribute.c:58-175) for one target sub-box -- order-preserving selection and packing
+#include "pf_distribute_boxes.h"  // PfDistTable, PF_DIST_GROUP_WAVES: the box table (plain C++, also compiled by a CPU test)
+#define PF_DIST_MAX_WORDS 56     // 4-byte words of a record the LDS-staged pack holds (records up to 224 bytes: 56 KB of LDS per workgroup)
+struct PfDistScratch {                   // device memory of one call (pf_dist_release)
+  unsigned int *map;                     // the caller's map, null: every bit set
+  unsigned long long *masks;             // [ngroups * PF_DIST_GROUP_WAVES] ballots
+  unsigned int *counts;                  // [ngroups]
+  unsigned long long *offs;              // [ngroups + 1] exclusive scan; the last one is the total
+};
+// the record as 4-byte words: src[j] = -1 zero, 0 Rmax, 1 + h word h of Fmax, 4 + 2 k + h word h of displacement column k (0..11)
+// (src[] is filled for records of up to PF_DIST_MAX_WORDS words; the named words alone, in named_off / named_src, for any stride)
+struct PfDistRecord { int nwords, nnamed; int named_off[28]; signed char named_src[28]; signed char src[PF_DIST_MAX_WORDS]; };
+// 0 ok; 1: len[*bad] outside [1, n]; 2: more than 2^32 cells
+int pf_dist_table(int n, int x0, int nxl, const pf_subbox *sub, PfDistTable *t, int *bad);
+// 0 ok; 1: stride or an offset is not a multiple of four, or a field leaves the record; 2: fields overlap
+int pf_dist_record(int pb, const pf_product_layout *l, PfDistRecord *r);
+// flag pass + scan: *count = cells taken.  Synchronises the stream (the count sizes what follows)
+int pf_dist_select(const PfDistTable &t, int pb, const void *fmax, double flast, const unsigned int *map_host, PfDistScratch *s,
+                   hipStream_t st, unsigned long long *count);
+// records [first, first + cnt) of the selection: aos (null: none; cnt records of `stride` bytes), frag_pos and cell_index (null: none).
+// lds: records staged in LDS and written as contiguous words (needs r.nwords <= PF_DIST_MAX_WORDS); else one lane per record into a
+// cleared aos
+int pf_dist_pack(const PfDistTable &t, const PfDistScratch &s, int pb, const void *fmax, const int *rmax, const void *vel12,
+                 size_t ncell_total, const PfDistRecord &r, size_t stride, unsigned long long first, unsigned long long cnt, char *aos,
+                 unsigned int *frag_pos, unsigned int *cell_index, bool lds, hipStream_t st);
+void pf_dist_release(PfDistScratch *s);
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);
