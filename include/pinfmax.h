@@ -352,6 +352,31 @@ int pf_distribute(pf_ctx *ctx, double flast, const pf_subbox *sub, const unsigne
    of an n^3 box, host, index z + n*(y + n*x_local); returns frag_pos and the local cell index of each taken cell */
 int pf_debug_distribute(int n, int x0, int nxl, const float *fmax_host, double flast, const pf_subbox *sub, const unsigned int *map,
                         size_t capacity, unsigned int *frag_pos, unsigned int *cell_index, size_t *count);
+/* The call of fragment() (src/fragment.c:193-346) that follows distribute(): sort_and_organize() (:484-520).  The reference sorts
+   an index array by descending Fmax (index_compare_F, :118-126), moves frag[] and frag_pos[] into that order (reorder, :533-564),
+   sorts again by frag_pos (index_compare_P, :128-136) and leaves sorted_pos[] / indices[] for find_location() (:592-603).  State
+   after it over N records: frag[i].Fmax non-increasing; sorted_pos[p] = frag_pos[indices[p]] strictly ascending (frag_pos is
+   unique within a sub-box; equal positions, which only a caller of pf_organize can supply, keep their order).  qsort leaves the
+   order of equal Fmax unspecified: here, as in pf_select_sorted, ties keep the order of the input (distribute()'s), -0.0 ties
+   with +0.0, and NaN -- which pf_distribute never stores -- goes last, after -inf.
+   pf_distribute_sorted = distribute() + sort_and_organize() for this rank's contribution to one target sub-box, straight from the
+   columns: selection, map, layout, zero-fill and *count / capacity as pf_distribute; frag / frag_pos receive the first
+   min(*count, capacity) records of the SORTED order and sorted_pos / indices describe exactly those records.  Any output may be
+   NULL.  When this rank is the only contributor (one rank; or a sub-box inside its own slab) the four arrays are the
+   reference's state after sort_and_organize().  2^31 records or more are refused: indices is int as in the reference. */
+int pf_distribute_sorted(pf_ctx *ctx, double flast, const pf_subbox *sub, const unsigned int *map, const pf_product_layout *layout,
+                         size_t capacity, void *frag, unsigned int *frag_pos, unsigned int *sorted_pos, int *indices, size_t *count);
+/* sort_and_organize() (src/fragment.c:484-520) on arrays the caller already holds -- the contributions of several ranks to one
+   sub-box, concatenated in distribute()'s order: frag (records of layout->stride bytes, Fmax of the context's precision at
+   layout->off_Fmax >= 0) and frag_pos are reordered in place; sorted_pos / indices (each may be NULL) as above.  The records
+   travel to one device buffer of count * stride bytes and back in the hand-off pieces; when that buffer and the sort's scratch
+   cannot be allocated the call fails, says how many bytes it needs and has touched nothing. */
+int pf_organize(pf_ctx *ctx, const pf_product_layout *layout, size_t count, void *frag, unsigned int *frag_pos,
+                unsigned int *sorted_pos, int *indices);
+/* test tap without a context: the ordering alone (index_compare_F then index_compare_P, src/fragment.c:118-136) on a caller's fp32
+   Fmax and frag_pos; order[i] = input index of record i of the sorted order */
+int pf_debug_organize(size_t count, const float *fmax, const unsigned int *frag_pos,
+                      unsigned int *order /* new -> old */, unsigned int *sorted_pos, int *indices);
 /* Per-particle payload of one block of the "timeless snapshot" (write_timeless_snapshot, src/write_snapshot.c:207-342)
    for this rank's slab, from the SoA columns in HBM: name = "ID  " (1 + global index as MYIDTYPE of id_bytes = 4 or 8,
    :648-664), "FMAX" float, "RMAX" int, "ZEL " / "2LPT" / "31PT" / "32PT" float[3] per particle (:700-855). */

@@ -105,6 +105,10 @@ PROTOTYPES = {
                                 C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]),
     "pf_debug_distribute": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_double, C.POINTER(SubBox), C.POINTER(C.c_uint),
                                       C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]),
+    "pf_distribute_sorted": (C.c_int, [_vp, C.c_double, C.POINTER(SubBox), C.POINTER(C.c_uint), C.POINTER(ProductLayout), C.c_size_t, _vp,
+                                       C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "pf_organize": (C.c_int, [_vp, C.POINTER(ProductLayout), C.c_size_t, _vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int)]),
+    "pf_debug_organize": (C.c_int, [C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int)]),
     "pf_set_collapse_model": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "pf_set_modified_gravity": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "pf_set_tabulated_ct": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),

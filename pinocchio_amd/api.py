@@ -107,6 +107,25 @@ def debug_distribute(fmax_slab: np.ndarray, x0: int, flast: float, start, length
     return pos[:m], idx[:m], int(cnt.value)
 
 
+def debug_organize(fmax: np.ndarray, frag_pos: np.ndarray):
+    """the ordering of sort_and_organize (src/fragment.c:484-520) by the device kernels on a caller's fp32 Fmax and frag_pos
+    -> (order, sorted_pos, indices): order[i] = input index of record i of the sorted order (descending Fmax, ties in input order,
+    NaN last), sorted_pos ascending = frag_pos[order][indices]"""
+    L = _lib.load()
+    f = np.ascontiguousarray(fmax, dtype=np.float32).ravel()
+    p = np.ascontiguousarray(frag_pos, dtype=np.uint32).ravel()
+    if f.size != p.size:
+        raise ValueError(f"{f.size} Fmax for {p.size} positions")
+    order = np.empty(f.size, dtype=np.uint32)
+    spos = np.empty(f.size, dtype=np.uint32)
+    ind = np.empty(f.size, dtype=np.int32)
+    if L.pf_debug_organize(f.size, f.ctypes.data_as(C.POINTER(C.c_float)), p.ctypes.data_as(C.POINTER(C.c_uint)),
+                           order.ctypes.data_as(C.POINTER(C.c_uint)), spos.ctypes.data_as(C.POINTER(C.c_uint)),
+                           ind.ctypes.data_as(C.POINTER(C.c_int))):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_organize failed")
+    return order, spos, ind
+
+
 class Fmax:
     """One rank's context: an x-slab of an n^3 grid on one MI355X."""
 
@@ -363,6 +382,52 @@ class Fmax:
         if dtype is not None:
             rec = rec.view(dtype).reshape(m)
         return rec, pos[:m], int(cnt.value)
+
+    def distribute_sorted(self, flast: float, start, length, map=None, layout=None, capacity=None):
+        """distribute() followed by sort_and_organize() (src/fragment.c:484-520) for this rank's contribution to the sub-box:
+        the records of distribute() by descending Fmax (ties in distribute()'s order) -> (records, frag_pos, sorted_pos, indices,
+        count), with sorted_pos ascending = frag_pos[indices] (what find_location, :592-603, searches).  Arguments as
+        distribute(); with a capacity below the count the first `capacity` records of the sorted order come back and
+        sorted_pos / indices describe those.  Not collective."""
+        sub = _subbox(start, length)
+        keep, mp = _distmap(map, length)
+        dtype = None
+        if layout is None:
+            layout, dtype = self.product_layout()
+        cnt = C.c_size_t()
+        if capacity is None:
+            self._chk(self.L.pf_distribute_sorted(self.h, float(flast), C.byref(sub), mp, C.byref(layout), 0, None, None, None, None, C.byref(cnt)))
+            capacity = cnt.value
+        capacity = int(capacity)
+        rec = np.zeros((capacity, layout.stride), dtype=np.uint8)
+        pos = np.empty(capacity, dtype=np.uint32)
+        spos = np.empty(capacity, dtype=np.uint32)
+        ind = np.empty(capacity, dtype=np.int32)
+        self._chk(self.L.pf_distribute_sorted(self.h, float(flast), C.byref(sub), mp, C.byref(layout), capacity, rec.ctypes.data_as(C.c_void_p),
+                                              pos.ctypes.data_as(C.POINTER(C.c_uint)), spos.ctypes.data_as(C.POINTER(C.c_uint)),
+                                              ind.ctypes.data_as(C.POINTER(C.c_int)), C.byref(cnt)))
+        m = min(cnt.value, capacity)
+        rec = rec[:m]
+        if dtype is not None:
+            rec = rec.view(dtype).reshape(m)
+        return rec, pos[:m], spos[:m], ind[:m], int(cnt.value)
+
+    def organize(self, records: np.ndarray, frag_pos: np.ndarray, layout=None):
+        """sort_and_organize() (src/fragment.c:484-520) on records the caller holds (contributions of several ranks to one
+        sub-box, concatenated): `records` (a structured array of product_layout(), or rows of layout.stride bytes) and `frag_pos`
+        (uint32) are reordered IN PLACE by descending Fmax, ties in input order -> (sorted_pos, indices)"""
+        if layout is None:
+            layout, _ = self.product_layout()
+        count = len(frag_pos)
+        if not (records.flags.c_contiguous and records.flags.writeable and records.nbytes == count * layout.stride):
+            raise ValueError(f"records of {records.nbytes} bytes for {count} positions and a stride of {layout.stride}")
+        if not (frag_pos.dtype == np.uint32 and frag_pos.flags.c_contiguous and frag_pos.flags.writeable):
+            raise ValueError("frag_pos must be a contiguous writeable uint32 array")
+        spos = np.empty(count, dtype=np.uint32)
+        ind = np.empty(count, dtype=np.int32)
+        self._chk(self.L.pf_organize(self.h, C.byref(layout), count, records.ctypes.data_as(C.c_void_p), frag_pos.ctypes.data_as(C.POINTER(C.c_uint)),
+                                     spos.ctypes.data_as(C.POINTER(C.c_uint)), ind.ctypes.data_as(C.POINTER(C.c_int))))
+        return spos, ind
 
     def block(self, name: str, id_bytes: int = 4) -> np.ndarray:
         """one block of the timeless snapshot (src/write_snapshot.c:207-342) for this rank's slab"""

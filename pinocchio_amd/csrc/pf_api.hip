@@ -36,7 +36,7 @@ extern "C" int pf_rccl_link_count(void *link);
 
 // ------------------------------------------------------------------ errors --
 static thread_local char g_err[512] = "";
-static int pf_fail(int task, const char *fmt, ...) {
+int pf_fail(int task, const char *fmt, ...) {  // (pf_internal.h: pf_organize.hip reports through it too)
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
@@ -2046,7 +2046,7 @@ extern "C" int pf_debug_peaks(int n, const float *fmax_host, double flast, const
 }
 
 // ---- distribute() for one target sub-box (pf_distribute.hip) ----
-static int dist_table(int task, const char *who, int n, int x0, int nxl, const pf_subbox *sub, PfDistTable *t) {
+int pf_dist_table_checked(int task, const char *who, int n, int x0, int nxl, const pf_subbox *sub, PfDistTable *t) {
   int d = 0;
   const int why = pf_dist_table(n, x0, nxl, sub, t, &d);
   if (why == 1) return pf_fail(task, "%s: sub-box does not fit the box: len[%d] = %d outside [1, %d]", who, d, sub->len[d], n);
@@ -2063,7 +2063,7 @@ extern "C" int pf_distribute(pf_ctx *c, double flast, const pf_subbox *sub, cons
   if (!c || !sub || !count || (frag && !l)) return pf_fail(c ? c->rank : 0, "pf_distribute: null argument");
   if (!c->products_init) return pf_fail(c->rank, "pf_distribute: products not computed");
   PfDistTable t;
-  if (dist_table(c->rank, "pf_distribute", c->n, c->rank * c->nxl, c->nxl, sub, &t)) return 1;
+  if (pf_dist_table_checked(c->rank, "pf_distribute", c->n, c->rank * c->nxl, c->nxl, sub, &t)) return 1;
   PfDistRecord rec;
   memset(&rec, 0, sizeof(rec));
   size_t stride = 0;
@@ -2134,7 +2134,7 @@ extern "C" int pf_debug_distribute(int n, int x0, int nxl, const float *fmax_hos
   const size_t nc = (size_t)nxl * n * n;
   if (nc > 0xFFFFFFFFull) return pf_fail(0, "pf_debug_distribute: more than 2^32 cells in the slab");
   PfDistTable t;
-  if (dist_table(0, "pf_debug_distribute", n, x0, nxl, sub, &t)) return 1;
+  if (pf_dist_table_checked(0, "pf_debug_distribute", n, x0, nxl, sub, &t)) return 1;
   PfDistScratch s;
   memset(&s, 0, sizeof(s));
   DistGuard guard{&s};
@@ -2160,6 +2160,32 @@ extern "C" int pf_debug_distribute(int n, int x0, int nxl, const float *fmax_hos
   hipFree(d); hipFree(out);
   return rc ? pf_fail(0, "pf_debug_distribute: device pass failed") : 0;
 }
+
+// ---- what pf_organize.hip needs of a context (pf_internal.h): the context itself stays private to this file ----
+void pf_ctx_view(pf_ctx *c, PfCtxView *v) {
+  v->rank = c->rank; v->n = c->n; v->nxl = c->nxl; v->pb = c->pb;
+  v->products_init = c->products_init; v->distribute_lds = c->tune.distribute_lds;
+  v->fmax = c->fmax; v->vel12 = c->vel12; v->rmax = c->rmax; v->ncell = ncell(c); v->stream = c->stream;
+}
+int pf_ctx_velocities_ready(pf_ctx *c) { return velocities_ready(c); }
+int pf_ctx_handoff_begin(pf_ctx *c, PfHandoffView *v) {
+  PfHandoff *h;
+  if (handoff_get(c, &h)) return 1;
+  PFCHK(c, handoff_begin(c, h));
+  for (int b = 0; b < 2; b++) { v->st[b] = h->st[b]; v->pin[b] = h->pin[b]; v->dev[b] = handoff_dev(c, b); }
+  v->chunk = h->chunk;
+  return 0;
+}
+void pf_ctx_host_copy(pf_ctx *c, void *dst, const void *src, size_t bytes) {
+  char *d = (char *)dst; const char *s = (const char *)src;
+  c->handoff->pool->run(bytes, [=](size_t a, size_t e) { memcpy(d + a, s + a, e - a); });
+}
+int pf_ctx_d2h(pf_ctx *c, void *host, const void *src_dev, size_t bytes) { return handoff_d2h(c, (char *)host, (const char *)src_dev, bytes, 4, no_fill); }
+int pf_ctx_h2d(pf_ctx *c, void *dst_dev, const void *host, size_t bytes) { return handoff_h2d(c, (char *)dst_dev, (const char *)host, bytes); }
+void *pf_ctx_timer_begin(pf_ctx *c, int phase, double bytes, hipStream_t st) {
+  return phase ? (void *)new PhaseTimer(c, 3, st) : (void *)new KTimer(c, KS_DISTRIBUTE, bytes, st);
+}
+void pf_ctx_timer_end(void *t, int phase) { if (phase) delete (PhaseTimer *)t; else delete (KTimer *)t; }
 
 // per-particle payload of one block of the timeless snapshot (src/write_snapshot.c:207-342, 620-855)
 extern "C" int pf_get_block(pf_ctx *c, const char *name, int id_bytes, void *host) {

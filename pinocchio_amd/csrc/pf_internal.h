@@ -266,6 +266,34 @@ int pf_dist_pack(const PfDistTable &t, const PfDistScratch &s, int pb, const voi
                  size_t ncell_total, const PfDistRecord &r, size_t stride, unsigned long long first, unsigned long long cnt, char *aos,
                  unsigned int *frag_pos, unsigned int *cell_index, bool lds, hipStream_t st);
 void pf_dist_release(PfDistScratch *s);
+// ---- pf_organize.hip: sort_and_organize() (src/fragment.c:484-520); it holds its own extern "C" entry points and sees a context
+// through these (pf_api.hip) ----
+int pf_fail(int task, const char *fmt, ...);   // sets pf_last_error, prints "ERROR on task %d: ...", returns 1
+int pf_dist_table_checked(int task, const char *who, int n, int x0, int nxl, const pf_subbox *sub, PfDistTable *t);  // pf_dist_table + message
+struct PfCtxView {
+  int rank, n, nxl, pb;
+  bool products_init, distribute_lds;
+  const void *fmax, *vel12; const int *rmax;
+  size_t ncell;           // cells of the slab
+  hipStream_t stream;
+};
+void pf_ctx_view(pf_ctx *c, PfCtxView *v);
+int pf_ctx_velocities_ready(pf_ctx *c);
+// the hand-off machinery (pf_api.hip PfHandoff): two streams that start behind the compute stream, a pinned buffer and a staging
+// field of the device for each, `chunk` bytes long
+struct PfHandoffView { hipStream_t st[2]; char *pin[2], *dev[2]; size_t chunk; };
+int pf_ctx_handoff_begin(pf_ctx *c, PfHandoffView *v);
+void pf_ctx_host_copy(pf_ctx *c, void *dst, const void *src, size_t bytes);          // by the host threads of the hand-off
+int pf_ctx_d2h(pf_ctx *c, void *host, const void *src_dev, size_t bytes);             // device array -> pageable memory, in pieces
+int pf_ctx_h2d(pf_ctx *c, void *dst_dev, const void *host, size_t bytes);
+// a kernel timer of the "distribute" class (phase 0) or the memory-transfer phase timer (phase 1) around a scope
+void *pf_ctx_timer_begin(pf_ctx *c, int phase, double bytes, hipStream_t st);
+void pf_ctx_timer_end(void *t, int phase);
+struct PfScopedTimer {
+  void *t; int phase;
+  PfScopedTimer(pf_ctx *c, int phase_, double bytes = 0, hipStream_t st = nullptr) : t(pf_ctx_timer_begin(c, phase_, bytes, st)), phase(phase_) {}
+  ~PfScopedTimer() { pf_ctx_timer_end(t, phase); }
+};
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);
