@@ -377,6 +377,65 @@ int pf_organize(pf_ctx *ctx, const pf_product_layout *layout, size_t count, void
    Fmax and frag_pos; order[i] = input index of record i of the sorted order */
 int pf_debug_organize(size_t count, const float *fmax, const unsigned int *frag_pos,
                       unsigned int *order /* new -> old */, unsigned int *sorted_pos, int *indices);
+/* The maps of fragment() (src/fragment.c:193-346) on the device: frag_map and frag_map_update as ONE resident object, so that the
+   two-turn loop of the default (non-CLASSIC_FRAGMENTATION) build uploads no map and builds none on the host.  A pf_map holds two
+   bit arrays of pf_map_length() = subbox.maplength = ceil(Lx Ly Lz / 32) words over box->len = subbox.Lgwbl: CURRENT (frag_map)
+   and UPDATE (frag_map_update), both zero after pf_map_create.  Bit pos = z + Lz (y + Ly x) (COORD_TO_INDEX, UINTLEN = 32) is
+   bit pos & 31 of word pos >> 5; the unused bits of the last word stay zero through every call.
+   pf_map_create: box = subbox.stabl, subbox.Lgwbl, subbox.safe.  With a context a direction is periodic (subbox.pbc) when
+   len[d] == n, the map lives on the context's device and every call is ordered on the context's stream; ctx may be NULL
+   (context-free: current device, default stream; such a map serves the pf_map_* calls only) and a direction is then periodic
+   when safe[d] == 0.  Refused: len[d] outside [1, n] (2048 without a context); more than 2^32 cells; safe[d] < 1 (or 2 safe >
+   len) in a direction that is not periodic -- create_map() would start at safe - 1 = -1 --; safe[d] != 0 in a periodic one.
+   pf_map_fill_box = create_map() (:708-751): UPDATE := zero, then per direction the range [safe - 1, Lgrid + safe + 1) with
+   Lgrid = len - 2 safe, [0, len) when periodic: the well resolved region plus one layer.
+   pf_map_update = update_map() (src/build_groups.c:2246-2318) over the groups the caller passes (FILAMENT + 1 .. ngroups - 1 of
+   the quick catalogue): pos[3 g ..] = groups[].Pos in sub-box coordinates, mass[g] = groups[].Mass.  UPDATE := zero; for every
+   group c = (int)(pos + 0.5) and size = (int)(boundary_layer_factor * pow((double)mass / 4.188790205, 0.333333333333333) + 0.5)
+   are computed on the HOST with the reference's own libm calls, and the cube [c - size, c + size)^3 is visited: a coordinate
+   outside [0, len) wraps ONCE in a periodic direction, otherwise the cell counts into nadd[1] and is skipped -- before the sphere
+   test, so nadd[1] counts cells of the cube, not of the sphere; a cell whose CURRENT bit is clear and whose unwrapped offset has
+   rr <= size^2 gets its UPDATE bit and counts into nadd[0].  nadd[0] counts WITH MULTIPLICITY: a cell that two spheres cover
+   counts twice, because the test reads frag_map and not frag_map_update.  (The log lines "Requesting %Ld particles from the
+   boundary layer" / "... lie beyond the boundary layer".)  The counts are 64-bit; the reference's unsigned int nadd[] wraps at
+   2^32.  ngroups = 0 is valid.  Refused, with nothing changed: in a periodic direction a group with size > len[d] or c outside
+   [0, len[d]] (the reference indexes out of bounds after its single wrap); a size beyond 16384; a position that is no number.
+   Words and counts do not depend on the schedule (bitwise reproducible).  PF_MAP_WORDS=0, read by pf_map_create, selects the
+   one-atomic-per-bit form of the kernel for that map (A/B; same results).
+   pf_map_commit: CURRENT = UPDATE (merge 0: "frag_map = frag_map_update", turn 0, :304-306) or CURRENT |= UPDATE (merge != 0,
+   turn 1, :307-309).  pf_map_get / pf_map_set move the pf_map_length() words of one array to / from the host (through the
+   context's hand-off pieces): how the map of a target sub-box reaches the device of a rank that sends to it -- get on the
+   target, the caller's transport, create + set on the sender.  pf_map_count: the number of set bits, an upper bound of what a
+   distribute call with that array stores. */
+typedef struct pf_map pf_map;
+#define PF_MAP_CURRENT 0   /* frag_map */
+#define PF_MAP_UPDATE 1    /* frag_map_update */
+int pf_map_create(pf_ctx *ctx, const pf_peak_region *box, pf_map **m);
+void pf_map_destroy(pf_map *m);                  /* before pf_destroy of its context */
+size_t pf_map_length(const pf_map *m);
+int pf_map_fill_box(pf_map *m);
+int pf_map_update(pf_map *m, size_t ngroups, const double *pos /* [3 * ngroups] */, const int *mass, double boundary_layer_factor,
+                  unsigned long long nadd[2]);
+int pf_map_commit(pf_map *m, int merge);
+int pf_map_get(pf_map *m, int which, unsigned int *words);
+int pf_map_set(pf_map *m, int which, const unsigned int *words);
+int pf_map_count(pf_map *m, int which, unsigned long long *bits);
+/* measurement aid (profiles/tools/map_time.py): the atomicOr the last pf_map_update of this map issued -- one per touched word of a
+   row, or with PF_MAP_WORDS=0 one per requested cell (= nadd[0]).  Only for a map created under PF_MAP_STATS=1, which selects
+   kernel instantiations that count; the default ones carry no counter and the call refuses */
+int pf_debug_map_atomics(const pf_map *m, unsigned long long *atomics);
+/* pf_distribute / pf_distribute_sorted with sub = (box.start, box.len) of the map and the named array (PF_MAP_CURRENT /
+   PF_MAP_UPDATE) read where it lies: nothing is uploaded.  The map must have been created with this context.  Results are those of
+   the host-map calls given the same words. */
+int pf_distribute_map(pf_ctx *ctx, double flast, pf_map *m, int which, const pf_product_layout *layout, size_t capacity, void *frag,
+                      unsigned int *frag_pos, size_t *count);
+int pf_distribute_sorted_map(pf_ctx *ctx, double flast, pf_map *m, int which, const pf_product_layout *layout, size_t capacity,
+                             void *frag, unsigned int *frag_pos, unsigned int *sorted_pos, int *indices, size_t *count);
+/* count_peaks() over the STORED set of the map's box: a cell is stored when its bit is set AND Fmax >= flast, and a neighbour
+   that is not stored vetoes nothing (:678-682) -- pf_count_peaks with a region takes every cell of the region with Fmax >= flast
+   for stored.  Region (= the map's box), border skipping, well resolved test, slab halos and sums as pf_count_peaks; collective,
+   every rank holding the same words.  peaks[0] is the reference's Npeaks ("found %d peaks") of either turn. */
+int pf_count_peaks_map(pf_ctx *ctx, double flast, pf_map *m, int which, unsigned long long peaks[2]);
 /* Per-particle payload of one block of the "timeless snapshot" (write_timeless_snapshot, src/write_snapshot.c:207-342)
    for this rank's slab, from the SoA columns in HBM: name = "ID  " (1 + global index as MYIDTYPE of id_bytes = 4 or 8,
    :648-664), "FMAX" float, "RMAX" int, "ZEL " / "2LPT" / "31PT" / "32PT" float[3] per particle (:700-855). */

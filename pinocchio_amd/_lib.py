@@ -16,6 +16,8 @@ MAX_SMOOTH = 64
 
 FLAG_TIMING = 1
 FLAG_DOUBLE_PRODUCTS = 2
+MAP_CURRENT = 0   # frag_map
+MAP_UPDATE = 1    # frag_map_update
 
 
 class Config(C.Structure):
@@ -109,6 +111,21 @@ PROTOTYPES = {
                                        C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "pf_organize": (C.c_int, [_vp, C.POINTER(ProductLayout), C.c_size_t, _vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int)]),
     "pf_debug_organize": (C.c_int, [C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int)]),
+    "pf_map_create": (C.c_int, [_vp, C.POINTER(PeakRegion), C.POINTER(_vp)]),
+    "pf_map_destroy": (None, [_vp]),
+    "pf_map_length": (C.c_size_t, [_vp]),
+    "pf_map_fill_box": (C.c_int, [_vp]),
+    "pf_map_update": (C.c_int, [_vp, C.c_size_t, _dp, C.POINTER(C.c_int), C.c_double, C.POINTER(C.c_ulonglong)]),
+    "pf_map_commit": (C.c_int, [_vp, C.c_int]),
+    "pf_map_get": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint)]),
+    "pf_map_set": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint)]),
+    "pf_map_count": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "pf_debug_map_atomics": (C.c_int, [_vp, C.POINTER(C.c_ulonglong)]),
+    "pf_distribute_map": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.POINTER(ProductLayout), C.c_size_t, _vp, C.POINTER(C.c_uint),
+                                    C.POINTER(C.c_size_t)]),
+    "pf_distribute_sorted_map": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.POINTER(ProductLayout), C.c_size_t, _vp, C.POINTER(C.c_uint),
+                                           C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "pf_count_peaks_map": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.POINTER(C.c_ulonglong)]),
     "pf_set_collapse_model": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "pf_set_modified_gravity": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "pf_set_tabulated_ct": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),

@@ -8,6 +8,7 @@ GPU; numpy is only the host container of inputs and outputs.
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -126,6 +127,99 @@ def debug_organize(fmax: np.ndarray, frag_pos: np.ndarray):
     return order, spos, ind
 
 
+_WHICH = {"current": _lib.MAP_CURRENT, "update": _lib.MAP_UPDATE}
+
+
+def _which(which):
+    """"current" (frag_map) / "update" (frag_map_update), or the integer itself (the library refuses one that names no array)"""
+    return _WHICH[which] if isinstance(which, str) else int(which)
+
+
+class FragMap:
+    """The two maps of fragment() (src/fragment.c:193-346) resident on the device (pf_map): CURRENT = frag_map and UPDATE =
+    frag_map_update over the sub-box (start, length, safe) = (subbox.stabl, subbox.Lgwbl, subbox.safe).  ctx: the Fmax context
+    whose distribute / count_peaks calls read the map (a direction is periodic when length == n); None: context-free, a direction
+    is periodic when safe == 0.  A context manager: the map is destroyed on exit (before its context)."""
+
+    def __init__(self, start, length, safe, ctx=None):
+        self.L = _lib.load()
+        self.ctx = ctx
+        self.start, self.length, self.safe = tuple(map(int, start)), tuple(map(int, length)), tuple(map(int, safe))
+        self.h = None
+        h = C.c_void_p()
+        rg = _region((self.start, self.length, self.safe))
+        self._chk(self.L.pf_map_create(ctx.h if ctx is not None else None, C.byref(rg), C.byref(h)))
+        self.h = h
+        self.nwords = int(self.L.pf_map_length(self.h))
+        if ctx is not None:
+            ctx._maps.add(self)        # the context destroys the maps that are still open before itself (Fmax.close)
+
+    def _chk(self, rc):
+        if rc:
+            raise PinfmaxError(self.L.pf_last_error().decode() or f"error {rc}")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.pf_map_destroy(self.h)
+            self.h = None
+        if self.ctx is not None:
+            self.ctx._maps.discard(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def fill_box(self):
+        """create_map() (src/fragment.c:708-751): UPDATE := the well resolved box plus one layer"""
+        self._chk(self.L.pf_map_fill_box(self.h))
+
+    def update(self, pos, mass, boundary_layer_factor: float):
+        """update_map() (src/build_groups.c:2246-2318): UPDATE := the spheres of the groups (pos [ngroups][3] in sub-box
+        coordinates, mass [ngroups] int) that CURRENT does not hold -> (nadd0, nadd1): cells requested (with multiplicity) and
+        cube cells beyond the boundary layer"""
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        mass = np.ascontiguousarray(mass, dtype=np.int32).ravel()
+        if len(pos) != len(mass):
+            raise ValueError(f"{len(pos)} positions for {len(mass)} masses")
+        out = (C.c_ulonglong * 2)()
+        self._chk(self.L.pf_map_update(self.h, len(mass), _dp(pos), mass.ctypes.data_as(C.POINTER(C.c_int)), float(boundary_layer_factor), out))
+        return int(out[0]), int(out[1])
+
+    def commit(self, merge):
+        """CURRENT = UPDATE (merge false: turn 0) or CURRENT |= UPDATE (merge true: turn 1), src/fragment.c:304-309"""
+        self._chk(self.L.pf_map_commit(self.h, 1 if merge else 0))
+
+    def words(self, which="current") -> np.ndarray:
+        w = np.empty(self.nwords, dtype=np.uint32)
+        self._chk(self.L.pf_map_get(self.h, _which(which), w.ctypes.data_as(C.POINTER(C.c_uint))))
+        return w
+
+    def set_words(self, which, w):
+        w = np.ascontiguousarray(w, dtype=np.uint32).ravel()
+        if w.size != self.nwords:
+            raise ValueError(f"{w.size} words for a map of {self.nwords}")
+        self._chk(self.L.pf_map_set(self.h, _which(which), w.ctypes.data_as(C.POINTER(C.c_uint))))
+
+    def atomics(self) -> int:
+        """atomicOr issued by the last update() of a map created under PF_MAP_STATS=1 (measurement aid)"""
+        out = C.c_ulonglong()
+        self._chk(self.L.pf_debug_map_atomics(self.h, C.byref(out)))
+        return int(out.value)
+
+    def count(self, which="current") -> int:
+        out = C.c_ulonglong()
+        self._chk(self.L.pf_map_count(self.h, _which(which), C.byref(out)))
+        return int(out.value)
+
+
 class Fmax:
     """One rank's context: an x-slab of an n^3 grid on one MI355X."""
 
@@ -141,6 +235,7 @@ class Fmax:
         self._chk(self.L.pf_create(C.byref(h), C.byref(cfg)))
         self.h = h
         self._keep = []
+        self._maps = weakref.WeakSet()  # open FragMaps bound to this context: pf_map_destroy must come before pf_destroy
 
     # -- plumbing ---------------------------------------------------------
     def _chk(self, rc):
@@ -149,6 +244,8 @@ class Fmax:
 
     def close(self):
         if getattr(self, "h", None):
+            for m in list(getattr(self, "_maps", ())):
+                m.close()
             self.L.pf_destroy(self.h)
             self.h = None
 
@@ -327,11 +424,29 @@ class Fmax:
                                               f.ctypes.data_as(C.POINTER(C.c_float)), C.byref(cnt)))
         return idx, f
 
-    def count_peaks(self, flast: float, region=None):
+    def frag_map(self, start, length, safe) -> FragMap:
+        """a resident map of the sub-box (subbox.stabl, subbox.Lgwbl, subbox.safe) bound to this context"""
+        return FragMap(start, length, safe, ctx=self)
+
+    def _own_map(self, m, start=None, length=None):
+        if m.ctx is not self:
+            raise ValueError("the FragMap belongs to another context")
+        if (start is not None and tuple(map(int, start)) != m.start) or (length is not None and tuple(map(int, length)) != m.length):
+            raise ValueError(f"start {tuple(start)} / length {tuple(length)} disagree with the map's box {m.start} / {m.length}")
+
+    def count_peaks(self, flast: float, region=None, map=None, which="current"):
         """count_peaks (src/fragment.c:605-706): (peaks of the region, those in its well resolved part), summed over ranks.
-        region = (start[3], len[3], safe[3]) in global grid coordinates, None = the whole periodic box.  Collective."""
-        rg = _region(region)
+        region = (start[3], len[3], safe[3]) in global grid coordinates, None = the whole periodic box.  map = a FragMap of this
+        context: the count over the STORED set of the map's box (bit of `which` set and Fmax >= flast), the reference's Npeaks of
+        either turn.  Collective."""
         out = (C.c_ulonglong * 2)()
+        if map is not None:
+            if region is not None:
+                raise ValueError("a FragMap carries its own region")
+            self._own_map(map)
+            self._chk(self.L.pf_count_peaks_map(self.h, float(flast), map.h, _which(which), out))
+            return int(out[0]), int(out[1])
+        rg = _region(region)
         self._chk(self.L.pf_count_peaks(self.h, float(flast), C.byref(rg) if rg is not None else None, out))
         return int(out[0]), int(out[1])
 
@@ -356,56 +471,73 @@ class Fmax:
         lay.off_Vel, lay.off_Vel_2LPT, lay.off_Vel_3LPT_1, lay.off_Vel_3LPT_2 = 16, 40, 64, 88
         return lay, PRODUCT_DTYPE_DP
 
-    def distribute(self, flast: float, start, length, map=None, layout=None, capacity=None):
+    def distribute(self, flast: float, start, length, map=None, layout=None, capacity=None, which="current"):
         """This rank's contribution to the sub-box (start[3], length[3]) = (subbox.stabl, subbox.Lgwbl) in distribute()
         (src/distribute.c:58-175): the cells of intersection(this slab, sub-box) whose bit of `map` (uint32 words, None: every
         bit) is set and whose Fmax >= flast, in the reference's order -> (records, frag_pos, count).  layout None: the record of
         products() as a structured array; a _lib.ProductLayout: rows of `stride` bytes.  capacity None: room for all (a
         count-only call first); otherwise at most `capacity` entries are returned and count still says how many were taken.
-        Not collective."""
-        sub = _subbox(start, length)
-        keep, mp = _distmap(map, length)
+        map = a FragMap of this context: its array `which` ("current" / "update") is read on the device, nothing is uploaded;
+        start / length must be the map's.  Not collective."""
         dtype = None
         if layout is None:
             layout, dtype = self.product_layout()
+        if isinstance(map, FragMap):
+            self._own_map(map, start, length)
+
+            def call(cap, rec, pos, cnt):
+                return self.L.pf_distribute_map(self.h, float(flast), map.h, _which(which), C.byref(layout), cap, rec, pos, C.byref(cnt))
+        else:
+            sub = _subbox(start, length)
+            keep, mp = _distmap(map, length)
+
+            def call(cap, rec, pos, cnt):
+                return self.L.pf_distribute(self.h, float(flast), C.byref(sub), mp, C.byref(layout), cap, rec, pos, C.byref(cnt))
         cnt = C.c_size_t()
         if capacity is None:
-            self._chk(self.L.pf_distribute(self.h, float(flast), C.byref(sub), mp, C.byref(layout), 0, None, None, C.byref(cnt)))
+            self._chk(call(0, None, None, cnt))
             capacity = cnt.value
         capacity = int(capacity)
         rec = np.zeros((capacity, layout.stride), dtype=np.uint8)
         pos = np.empty(capacity, dtype=np.uint32)
-        self._chk(self.L.pf_distribute(self.h, float(flast), C.byref(sub), mp, C.byref(layout), capacity, rec.ctypes.data_as(C.c_void_p),
-                                       pos.ctypes.data_as(C.POINTER(C.c_uint)), C.byref(cnt)))
+        self._chk(call(capacity, rec.ctypes.data_as(C.c_void_p), pos.ctypes.data_as(C.POINTER(C.c_uint)), cnt))
         m = min(cnt.value, capacity)
         rec = rec[:m]
         if dtype is not None:
             rec = rec.view(dtype).reshape(m)
         return rec, pos[:m], int(cnt.value)
 
-    def distribute_sorted(self, flast: float, start, length, map=None, layout=None, capacity=None):
+    def distribute_sorted(self, flast: float, start, length, map=None, layout=None, capacity=None, which="current"):
         """distribute() followed by sort_and_organize() (src/fragment.c:484-520) for this rank's contribution to the sub-box:
         the records of distribute() by descending Fmax (ties in distribute()'s order) -> (records, frag_pos, sorted_pos, indices,
         count), with sorted_pos ascending = frag_pos[indices] (what find_location, :592-603, searches).  Arguments as
         distribute(); with a capacity below the count the first `capacity` records of the sorted order come back and
-        sorted_pos / indices describe those.  Not collective."""
-        sub = _subbox(start, length)
-        keep, mp = _distmap(map, length)
+        sorted_pos / indices describe those.  map = a FragMap: as in distribute().  Not collective."""
         dtype = None
         if layout is None:
             layout, dtype = self.product_layout()
+        if isinstance(map, FragMap):
+            self._own_map(map, start, length)
+
+            def call(cap, rec, pos, spos, ind, cnt):
+                return self.L.pf_distribute_sorted_map(self.h, float(flast), map.h, _which(which), C.byref(layout), cap, rec, pos, spos, ind, C.byref(cnt))
+        else:
+            sub = _subbox(start, length)
+            keep, mp = _distmap(map, length)
+
+            def call(cap, rec, pos, spos, ind, cnt):
+                return self.L.pf_distribute_sorted(self.h, float(flast), C.byref(sub), mp, C.byref(layout), cap, rec, pos, spos, ind, C.byref(cnt))
         cnt = C.c_size_t()
         if capacity is None:
-            self._chk(self.L.pf_distribute_sorted(self.h, float(flast), C.byref(sub), mp, C.byref(layout), 0, None, None, None, None, C.byref(cnt)))
+            self._chk(call(0, None, None, None, None, cnt))
             capacity = cnt.value
         capacity = int(capacity)
         rec = np.zeros((capacity, layout.stride), dtype=np.uint8)
         pos = np.empty(capacity, dtype=np.uint32)
         spos = np.empty(capacity, dtype=np.uint32)
         ind = np.empty(capacity, dtype=np.int32)
-        self._chk(self.L.pf_distribute_sorted(self.h, float(flast), C.byref(sub), mp, C.byref(layout), capacity, rec.ctypes.data_as(C.c_void_p),
-                                              pos.ctypes.data_as(C.POINTER(C.c_uint)), spos.ctypes.data_as(C.POINTER(C.c_uint)),
-                                              ind.ctypes.data_as(C.POINTER(C.c_int)), C.byref(cnt)))
+        self._chk(call(capacity, rec.ctypes.data_as(C.c_void_p), pos.ctypes.data_as(C.POINTER(C.c_uint)), spos.ctypes.data_as(C.POINTER(C.c_uint)),
+                       ind.ctypes.data_as(C.POINTER(C.c_int)), cnt))
         m = min(cnt.value, capacity)
         rec = rec[:m]
         if dtype is not None:

@@ -1974,22 +1974,38 @@ static int peak_params(pf_ctx *c, const char *who, double flast, const pf_peak_r
   return peak_halo(c, p, scratch);
 }
 
-extern "C" int pf_count_peaks(pf_ctx *c, double flast, const pf_peak_region *region, unsigned long long peaks[2]) {
-  if (!c || !peaks) return pf_fail(0, "pf_count_peaks: null argument");
+// map (device, null: none): the stored set is the map's bits among the cells with Fmax >= flast; region is then the map's box
+static int count_peaks_impl(pf_ctx *c, const char *who, double flast, const pf_peak_region *region, const unsigned int *map, unsigned long long peaks[2]) {
   PfPeakParams p;
   void *scratch = nullptr;
-  if (peak_params(c, "pf_count_peaks", flast, region, &p, &scratch)) { hipStreamSynchronize(c->stream); hipFree(scratch); return 1; }
+  if (peak_params(c, who, flast, region, &p, &scratch)) { hipStreamSynchronize(c->stream); hipFree(scratch); return 1; }
+  if (map) { p.map = map; for (int d = 0; d < 3; d++) p.mlen[d] = region->len[d]; }
   int rc;
   {
     KTimer t(c, KS_PEAKS, (double)ncell(c) * c->pb);
     rc = pf_launch_peaks(c->pb, p, c->stream);
   }
-  if (rc) { hipStreamSynchronize(c->stream); hipFree(scratch); return pf_fail(c->rank, "pf_count_peaks: launch failed"); }
+  if (rc) { hipStreamSynchronize(c->stream); hipFree(scratch); return pf_fail(c->rank, "%s: launch failed", who); }
   rc = allreduce_dev(c, c->hist, 2, 1);
   if (!rc && hipMemcpyAsync(peaks, c->hist, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = 1;
   if (hipStreamSynchronize(c->stream) != hipSuccess) rc = 1;
   hipFree(scratch);
-  return rc ? pf_fail(c->rank, "pf_count_peaks: reduction or copy failed") : 0;
+  return rc ? pf_fail(c->rank, "%s: reduction or copy failed", who) : 0;
+}
+
+extern "C" int pf_count_peaks(pf_ctx *c, double flast, const pf_peak_region *region, unsigned long long peaks[2]) {
+  if (!c || !peaks) return pf_fail(0, "pf_count_peaks: null argument");
+  return count_peaks_impl(c, "pf_count_peaks", flast, region, nullptr, peaks);
+}
+
+extern "C" int pf_count_peaks_map(pf_ctx *c, double flast, pf_map *m, int which, unsigned long long peaks[2]) {
+  const char *who = "pf_count_peaks_map";
+  if (!c || !peaks) return pf_fail(0, "%s: null argument", who);
+  PfMapView mv;
+  if (pf_map_view(who, c, c->rank, m, which, &mv)) return 1;
+  pf_peak_region rg;
+  for (int d = 0; d < 3; d++) { rg.start[d] = mv.start[d]; rg.len[d] = mv.len[d]; rg.safe[d] = mv.safe[d]; }
+  return count_peaks_impl(c, who, flast, &rg, mv.bits, peaks);
 }
 
 extern "C" int pf_select_peaks(pf_ctx *c, double flast, size_t capacity, unsigned int *cell_index, float *fmax, size_t *count) {
@@ -2058,19 +2074,20 @@ struct DistGuard { PfDistScratch *s; ~DistGuard() { pf_dist_release(s); } };
 // This rank's contribution to one sub-box.  Flag pass and scan on the compute stream, one 8-byte read-back for the count; then the
 // records leave through the hand-off machinery of pf_get_products: piece k is packed into one of the two staging fields (records,
 // then their frag_pos) and copied into its pinned buffer while the host threads move piece k - 1 into the caller's arrays.
-extern "C" int pf_distribute(pf_ctx *c, double flast, const pf_subbox *sub, const unsigned int *map, const pf_product_layout *l,
-                             size_t capacity, void *frag, unsigned int *frag_pos, size_t *count) {
-  if (!c || !sub || !count || (frag && !l)) return pf_fail(c ? c->rank : 0, "pf_distribute: null argument");
-  if (!c->products_init) return pf_fail(c->rank, "pf_distribute: products not computed");
+// map: on the host (uploaded by the selection), or map_dev: a resident one (pf_map.hip) read in place
+static int distribute_impl(const char *who, pf_ctx *c, double flast, const pf_subbox *sub, const unsigned int *map, const unsigned int *map_dev,
+                           const pf_product_layout *l, size_t capacity, void *frag, unsigned int *frag_pos, size_t *count) {
+  if (!c || !sub || !count || (frag && !l)) return pf_fail(c ? c->rank : 0, "%s: null argument", who);
+  if (!c->products_init) return pf_fail(c->rank, "%s: products not computed", who);
   PfDistTable t;
-  if (pf_dist_table_checked(c->rank, "pf_distribute", c->n, c->rank * c->nxl, c->nxl, sub, &t)) return 1;
+  if (pf_dist_table_checked(c->rank, who, c->n, c->rank * c->nxl, c->nxl, sub, &t)) return 1;
   PfDistRecord rec;
   memset(&rec, 0, sizeof(rec));
   size_t stride = 0;
   if (frag) {
     const int why = pf_dist_record(c->pb, l, &rec);
-    if (why == 1) return pf_fail(c->rank, "pf_distribute: bad layout: stride %zu and the offsets must be multiples of four, fields inside the record", l->stride);
-    if (why) return pf_fail(c->rank, "pf_distribute: fields of the layout overlap");
+    if (why == 1) return pf_fail(c->rank, "%s: bad layout: stride %zu and the offsets must be multiples of four, fields inside the record", who, l->stride);
+    if (why) return pf_fail(c->rank, "%s: fields of the layout overlap", who);
     stride = l->stride;
     if (l->off_Vel >= 0 || l->off_Vel_2LPT >= 0 || l->off_Vel_3LPT_1 >= 0 || l->off_Vel_3LPT_2 >= 0) PFCHK(c, velocities_ready(c));
   }
@@ -2081,8 +2098,8 @@ extern "C" int pf_distribute(pf_ctx *c, double flast, const pf_subbox *sub, cons
   unsigned long long total = 0;
   const double cells = 64.0 * (double)t.wave0[t.nbox];
   {
-    KTimer kt(c, KS_DISTRIBUTE, cells * (c->pb + 0.125 + (map ? 0.125 : 0.0)));
-    if (pf_dist_select(t, c->pb, c->fmax, flast, map, &s, c->stream, &total)) return pf_fail(c->rank, "pf_distribute: selection failed (out of memory?)");
+    KTimer kt(c, KS_DISTRIBUTE, cells * (c->pb + 0.125 + (map || map_dev ? 0.125 : 0.0)));
+    if (pf_dist_select(t, c->pb, c->fmax, flast, map, map_dev, &s, c->stream, &total)) return pf_fail(c->rank, "%s: selection failed (out of memory?)", who);
   }
   *count = (size_t)total;
   const size_t m = *count < capacity ? *count : capacity;
@@ -2091,7 +2108,7 @@ extern "C" int pf_distribute(pf_ctx *c, double flast, const pf_subbox *sub, cons
   if (handoff_get(c, &h)) return 1;
   PFCHK(c, handoff_begin(c, h));
   const size_t per = h->chunk / (stride + (frag_pos ? 4 : 0));
-  if (!per) return pf_fail(c->rank, "pf_distribute: a record of %zu bytes does not fit the staging pieces", stride);
+  if (!per) return pf_fail(c->rank, "%s: a record of %zu bytes does not fit the staging pieces", who, stride);
   const size_t np = (m + per - 1) / per;
   const bool lds = c->tune.distribute_lds && rec.nwords <= PF_DIST_MAX_WORDS;
   auto issue = [&](size_t k) -> int {
@@ -2127,6 +2144,35 @@ extern "C" int pf_distribute(pf_ctx *c, double flast, const pf_subbox *sub, cons
   return 0;
 }
 
+extern "C" int pf_distribute(pf_ctx *c, double flast, const pf_subbox *sub, const unsigned int *map, const pf_product_layout *l,
+                             size_t capacity, void *frag, unsigned int *frag_pos, size_t *count) {
+  return distribute_impl("pf_distribute", c, flast, sub, map, nullptr, l, capacity, frag, frag_pos, count);
+}
+
+// ... with a resident map (pf_map.hip): the sub-box is the map's box
+static int map_subbox(const char *who, pf_ctx *c, pf_map *m, int which, pf_subbox *sub, const unsigned int **bits) {
+  if (!c) return pf_fail(0, "%s: null argument", who);
+  PfMapView mv;
+  if (pf_map_view(who, c, c->rank, m, which, &mv)) return 1;
+  for (int d = 0; d < 3; d++) { sub->start[d] = mv.start[d]; sub->len[d] = mv.len[d]; }
+  *bits = mv.bits;
+  return 0;
+}
+extern "C" int pf_distribute_map(pf_ctx *c, double flast, pf_map *m, int which, const pf_product_layout *l, size_t capacity, void *frag,
+                                 unsigned int *frag_pos, size_t *count) {
+  pf_subbox sub;
+  const unsigned int *bits = nullptr;
+  if (map_subbox("pf_distribute_map", c, m, which, &sub, &bits)) return 1;
+  return distribute_impl("pf_distribute_map", c, flast, &sub, nullptr, bits, l, capacity, frag, frag_pos, count);
+}
+extern "C" int pf_distribute_sorted_map(pf_ctx *c, double flast, pf_map *m, int which, const pf_product_layout *l, size_t capacity, void *frag,
+                                        unsigned int *frag_pos, unsigned int *sorted_pos, int *indices, size_t *count) {
+  pf_subbox sub;
+  const unsigned int *bits = nullptr;
+  if (map_subbox("pf_distribute_sorted_map", c, m, which, &sub, &bits)) return 1;
+  return pf_distribute_sorted_impl("pf_distribute_sorted_map", c, flast, &sub, nullptr, bits, l, capacity, frag, frag_pos, sorted_pos, indices, count);
+}
+
 // context-free tap: flag pass, scan and the ordering part of the pack pass on a caller's slab of an fp32 field
 extern "C" int pf_debug_distribute(int n, int x0, int nxl, const float *fmax_host, double flast, const pf_subbox *sub, const unsigned int *map,
                                    size_t capacity, unsigned int *frag_pos, unsigned int *cell_index, size_t *count) {
@@ -2145,7 +2191,7 @@ extern "C" int pf_debug_distribute(int n, int x0, int nxl, const float *fmax_hos
   unsigned long long total = 0;
   int rc = 1;
   if (hipMalloc((void **)&d, nc * sizeof(float)) == hipSuccess && hipMemcpy(d, fmax_host, nc * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-      !pf_dist_select(t, 4, d, flast, map, &s, nullptr, &total)) {
+      !pf_dist_select(t, 4, d, flast, map, nullptr, &s, nullptr, &total)) {
     *count = (size_t)total;
     const size_t m = *count < capacity ? *count : capacity;
     rc = 0;

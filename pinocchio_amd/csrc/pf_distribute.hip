@@ -196,8 +196,8 @@ void pf_dist_release(PfDistScratch *s) {
   memset(s, 0, sizeof(*s));
 }
 
-int pf_dist_select(const PfDistTable &t, int pb, const void *fmax, double flast, const unsigned int *map_host, PfDistScratch *s,
-                   hipStream_t st, unsigned long long *count) {
+int pf_dist_select(const PfDistTable &t, int pb, const void *fmax, double flast, const unsigned int *map_host, const unsigned int *map_dev,
+                   PfDistScratch *s, hipStream_t st, unsigned long long *count) {
   memset(s, 0, sizeof(*s));
   *count = 0;
   if (!t.ngroups) return 0;   // the sub-box misses the slab
@@ -210,8 +210,9 @@ int pf_dist_select(const PfDistTable &t, int pb, const void *fmax, double flast,
                            hipMemcpyAsync(s->map, map_host, map_words * sizeof(unsigned int), hipMemcpyHostToDevice, st) == hipSuccess;
   if (!ok) { (void)hipGetLastError(); pf_dist_release(s); return 1; }
   const dim3 grid((unsigned int)t.ngroups), block(PF_DIST_BLOCK);
-  if (pb == 8) hipLaunchKernelGGL(k_dist_flag<double>, grid, block, 0, st, t, (const double *)fmax, dist_thr(flast, double()), s->map, s->masks, s->counts);
-  else hipLaunchKernelGGL(k_dist_flag<float>, grid, block, 0, st, t, (const float *)fmax, dist_thr(flast, float()), s->map, s->masks, s->counts);
+  const unsigned int *map = map_host ? s->map : map_dev;   // (a resident map, pf_map.hip, is read where it lies)
+  if (pb == 8) hipLaunchKernelGGL(k_dist_flag<double>, grid, block, 0, st, t, (const double *)fmax, dist_thr(flast, double()), map, s->masks, s->counts);
+  else hipLaunchKernelGGL(k_dist_flag<float>, grid, block, 0, st, t, (const float *)fmax, dist_thr(flast, float()), map, s->masks, s->counts);
   hipLaunchKernelGGL(k_dist_scan, dim3(1), dim3(1024), 0, st, s->counts, t.ngroups, s->offs);
   if (hipGetLastError() != hipSuccess ||
       hipMemcpyAsync(count, s->offs + t.ngroups, sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||

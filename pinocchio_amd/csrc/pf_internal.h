@@ -236,6 +236,8 @@ struct PfPeakParams {
   unsigned long long *counters;   // device: [0] peaks, [1] well resolved peaks, [2] key cursor
   unsigned long long *keys;       // null: count only
   size_t key_cap;
+  const unsigned int *map;        // non-null (device): the stored set is (bit of the map's box set) && Fmax >= flast; the region is that box
+  int mlen[3];                    // ... whose Lgwbl this is (its start is start[])
 };
 int pf_peak_region_setup(int n, const pf_peak_region *rg, PfPeakParams *p, int *bad);
 int pf_launch_peaks(int pb, const PfPeakParams &p, hipStream_t st);
@@ -257,8 +259,9 @@ int pf_dist_table(int n, int x0, int nxl, const pf_subbox *sub, PfDistTable *t, 
 // 0 ok; 1: stride or an offset is not a multiple of four, or a field leaves the record; 2: fields overlap
 int pf_dist_record(int pb, const pf_product_layout *l, PfDistRecord *r);
 // flag pass + scan: *count = cells taken.  Synchronises the stream (the count sizes what follows)
-int pf_dist_select(const PfDistTable &t, int pb, const void *fmax, double flast, const unsigned int *map_host, PfDistScratch *s,
-                   hipStream_t st, unsigned long long *count);
+// map_dev (with map_host null): a map that lies on the device already is read in place, nothing is uploaded and *s does not own it
+int pf_dist_select(const PfDistTable &t, int pb, const void *fmax, double flast, const unsigned int *map_host, const unsigned int *map_dev,
+                   PfDistScratch *s, hipStream_t st, unsigned long long *count);
 // records [first, first + cnt) of the selection: aos (null: none; cnt records of `stride` bytes), frag_pos and cell_index (null: none).
 // lds: records staged in LDS and written as contiguous words (needs r.nwords <= PF_DIST_MAX_WORDS); else one lane per record into a
 // cleared aos
@@ -294,6 +297,14 @@ struct PfScopedTimer {
   PfScopedTimer(pf_ctx *c, int phase_, double bytes = 0, hipStream_t st = nullptr) : t(pf_ctx_timer_begin(c, phase_, bytes, st)), phase(phase_) {}
   ~PfScopedTimer() { pf_ctx_timer_end(t, phase); }
 };
+// ---- pf_map.hip: the resident fragmentation maps; what the distribute and count_peaks entry points see of one ----
+struct PfMapView { int start[3], len[3], safe[3]; const unsigned int *bits; size_t words; };
+// refuses (message of `who`) a null map, a map of another context and a `which` that names no array
+int pf_map_view(const char *who, pf_ctx *c, int rank, pf_map *m, int which, PfMapView *v);
+// pf_distribute_sorted with the map on the host or (map_host null) on the device (pf_organize.hip)
+int pf_distribute_sorted_impl(const char *who, pf_ctx *c, double flast, const pf_subbox *sub, const unsigned int *map_host, const unsigned int *map_dev,
+                              const pf_product_layout *l, size_t capacity, void *frag, unsigned int *frag_pos, unsigned int *sorted_pos, int *indices,
+                              size_t *count);
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);

@@ -310,9 +310,9 @@ static unsigned int bits_for(unsigned long long cells) {   // positions lie belo
   return b;
 }
 
-extern "C" int pf_distribute_sorted(pf_ctx *c, double flast, const pf_subbox *sub, const unsigned int *map, const pf_product_layout *l, size_t capacity,
-                                    void *frag, unsigned int *frag_pos, unsigned int *sorted_pos, int *indices, size_t *count) {
-  const char *who = "pf_distribute_sorted";
+int pf_distribute_sorted_impl(const char *who, pf_ctx *c, double flast, const pf_subbox *sub, const unsigned int *map, const unsigned int *map_dev,
+                              const pf_product_layout *l, size_t capacity, void *frag, unsigned int *frag_pos, unsigned int *sorted_pos, int *indices,
+                              size_t *count) {
   if (!c) return pf_fail(0, "%s: null argument", who);
   PfCtxView v;
   pf_ctx_view(c, &v);
@@ -336,8 +336,8 @@ extern "C" int pf_distribute_sorted(pf_ctx *c, double flast, const pf_subbox *su
   unsigned long long total = 0;
   const double cells = 64.0 * (double)t.wave0[t.nbox];
   {
-    PfScopedTimer kt(c, 0, cells * (v.pb + 0.125 + (map ? 0.125 : 0.0)));
-    if (pf_dist_select(t, v.pb, v.fmax, flast, map, &s, v.stream, &total)) return pf_fail(v.rank, "%s: selection failed (out of memory?)", who);
+    PfScopedTimer kt(c, 0, cells * (v.pb + 0.125 + (map || map_dev ? 0.125 : 0.0)));
+    if (pf_dist_select(t, v.pb, v.fmax, flast, map, map_dev, &s, v.stream, &total)) return pf_fail(v.rank, "%s: selection failed (out of memory?)", who);
   }
   *count = (size_t)total;
   if (total > 0x7FFFFFFFull)
@@ -364,6 +364,11 @@ extern "C" int pf_distribute_sorted(pf_ctx *c, double flast, const pf_subbox *su
   if (index && org_index_leave(c, v, who, in, m, bits_for((unsigned long long)t.slen[0] * t.slen[1] * t.slen[2]), &o, sorted_pos, indices)) return 1;
   if (!frag && !frag_pos) { ORGHIP(v.rank, who, hipStreamSynchronize(v.stream)); return 0; }
   return org_leave(c, v, who, in, o.perm, rec, stride, m, frag, frag_pos, v.distribute_lds);
+}
+
+extern "C" int pf_distribute_sorted(pf_ctx *c, double flast, const pf_subbox *sub, const unsigned int *map, const pf_product_layout *l, size_t capacity,
+                                    void *frag, unsigned int *frag_pos, unsigned int *sorted_pos, int *indices, size_t *count) {
+  return pf_distribute_sorted_impl("pf_distribute_sorted", c, flast, sub, map, nullptr, l, capacity, frag, frag_pos, sorted_pos, indices, count);
 }
 
 extern "C" int pf_organize(pf_ctx *c, const pf_product_layout *l, size_t count, void *frag, unsigned int *frag_pos, unsigned int *sorted_pos, int *indices) {

@@ -16,9 +16,15 @@
 // that is examined has all six neighbours inside the region, at the global coordinates +-1 (mod n).
 // Counting: per-lane counters over the whole march, one 64-bit atomic per wavefront and counter at the end.  KEYS: the sort
 // keys of pf_select_sort.hip appended with one atomic per wavefront and plane.
+// MAP (pf_count_peaks_map): the stored set is a subset of the region's cells -- bit set in a resident map (pf_map.hip) of the region's
+// box AND Fmax >= Flast.  Every value passes through the map as it is loaded: a cell whose bit is clear, or that lies outside the
+// box, becomes NaN, which every comparison below already treats as "not stored, vetoes nothing".  The other instantiations do
+// not see the map at all (their arguments are the plain PkArgs).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
+
+#include <type_traits>
 
 #include "pf_internal.h"
 #include "pf_keys.h"
@@ -40,6 +46,11 @@ struct PkArgs {
   unsigned long long key_cap;
 };
 
+struct PkMapArgs : PkArgs {
+  const unsigned int *map;   // bit z + Lz (y + Ly x) of the box start[], mlen[]
+  int mlen[3];
+};
+
 // bit i of the result: coordinate c0 + i (global, mod n) lies in [lo, hi) of the region's own coordinates
 __device__ __forceinline__ unsigned int pk_range_mask(int c0, int count, int n, int start, int lo, int hi) {
   unsigned int m = 0;
@@ -51,8 +62,8 @@ __device__ __forceinline__ unsigned int pk_range_mask(int c0, int count, int n, 
   return m;
 }
 
-template <typename PR, int V, bool KEYS>
-__global__ void __launch_bounds__(PF_PEAK_BLOCK) k_peaks(PkArgs a, PR thr) {
+template <typename PR, int V, bool KEYS, bool MAP = false>
+__global__ void __launch_bounds__(PF_PEAK_BLOCK) k_peaks(typename std::conditional<MAP, PkMapArgs, PkArgs>::type a, PR thr) {
   constexpr int TY = PF_PEAK_TY;
   typedef PkVec<PR, V> Vec;
   const int n = a.n, nzv = n / V, nyg = (n + TY - 1) / TY;
@@ -93,6 +104,41 @@ __global__ void __launch_bounds__(PF_PEAK_BLOCK) k_peaks(PkArgs a, PR thr) {
     return xl < 0 ? (const PR *)a.halo_lo : xl >= a.nxl ? (const PR *)a.halo_hi : slab + (size_t)xl * plane;
   };
 
+  // MAP: the box coordinates of my rows (y-halo rows first and last) and cells (z-neighbours first and last), -1 outside the box
+  int my[MAP ? TY + 2 : 1], mz[MAP ? V + 2 : 1];
+  auto box_coord = [&](int g, int d) -> int {
+    if constexpr (MAP) {
+      int l = g % n - a.start[d];
+      if (l < 0) l += n;
+      return l < a.mlen[d] ? l : -1;
+    } else return 0;
+  };
+  // the value of the cell (lx, ly, lz) of the box as the stored set sees it
+  auto through = [&](PR f, int lx, int ly, int lz) -> PR {
+    if constexpr (MAP) {
+      if ((lx | ly | lz) < 0) return (PR)NAN;
+      const unsigned int pos = ((unsigned int)lx * (unsigned int)a.mlen[1] + (unsigned int)ly) * (unsigned int)a.mlen[2] + (unsigned int)lz;   // (< 2^32 cells)
+      return ((a.map[pos >> 5] >> (pos & 31u)) & 1u) ? f : (PR)NAN;
+    } else return f;
+  };
+  auto through_vec = [&](Vec v, int lx, int ly) -> Vec {
+    if constexpr (MAP) {
+#pragma unroll
+      for (int e = 0; e < V; e++) v.v[e] = through(v.v[e], lx, ly, mz[e + 1]);
+    }
+    return v;
+  };
+  auto plane_coord = [&](int xl) -> int { return box_coord(a.x0 + xl + n, 0); };
+  if constexpr (MAP) {
+    my[0] = box_coord(yb + n - 1, 1); my[TY + 1] = box_coord(yb + TY, 1);
+#pragma unroll
+    for (int r = 0; r < TY; r++) my[r + 1] = box_coord(yb + r, 1);
+    mz[0] = box_coord(z0 == 0 ? n - 1 : z0 - 1, 2); mz[V + 1] = box_coord(z0 + V == n ? 0 : z0 + V, 2);
+#pragma unroll
+    for (int e = 0; e < V; e++) mz[e + 1] = box_coord(z0 + e, 2);
+  }
+  int lxc = 0, lxn = 0;   // box x of the planes in cur and nxt
+
   unsigned int cnt = 0, cntg = 0;
   // planes x and x + 1 of the column in registers; of plane x - 1 only what it says about plane x: bit r V + e of `below` is set when
   // its cell is no smaller than the cell (r, e) of the plane in `cur`
@@ -100,19 +146,22 @@ __global__ void __launch_bounds__(PF_PEAK_BLOCK) k_peaks(PkArgs a, PR thr) {
   unsigned int below = 0;
   if (xa < xb) {
     const PR *pp = plane_of(xa - 1), *pc = plane_of(xa);
+    const int lxp = plane_coord(xa - 1);
+    lxc = plane_coord(xa);
 #pragma unroll
     for (int r = 0; r < TY; r++) {
-      const Vec prv = pk_load<PR, V>(pp + row[r]);
-      cur[r] = pk_load<PR, V>(pc + row[r]);
+      const Vec prv = through_vec(pk_load<PR, V>(pp + row[r]), lxp, my[MAP ? r + 1 : 0]);
+      cur[r] = through_vec(pk_load<PR, V>(pc + row[r]), lxc, my[MAP ? r + 1 : 0]);
 #pragma unroll
       for (int e = 0; e < V; e++) if (prv.v[e] >= cur[r].v[e]) below |= 1u << (r * V + e);
     }
   }
   for (int xl = xa; xl < xb; xl++) {
     const PR *pc = plane_of(xl), *pn = plane_of(xl + 1);
+    lxn = plane_coord(xl + 1);
 #pragma unroll
-    for (int r = 0; r < TY; r++) nxt[r] = pk_load<PR, V>(pn + row[r]);
-    const Vec hlo = pk_load<PR, V>(pc + row_lo), hhi = pk_load<PR, V>(pc + row_hi);
+    for (int r = 0; r < TY; r++) nxt[r] = through_vec(pk_load<PR, V>(pn + row[r]), lxn, my[MAP ? r + 1 : 0]);
+    const Vec hlo = through_vec(pk_load<PR, V>(pc + row_lo), lxc, my[0]), hhi = through_vec(pk_load<PR, V>(pc + row_hi), lxc, my[MAP ? TY + 1 : 0]);
     int gx = a.x0 + xl - a.start[0]; if (gx < 0) gx += n;
     const bool xok = gx >= a.lo[0] && gx < a.hi[0], xgood = gx >= a.glo[0] && gx < a.ghi[0];
     unsigned int pm = 0, gm = 0, below_next = 0;
@@ -120,8 +169,8 @@ __global__ void __launch_bounds__(PF_PEAK_BLOCK) k_peaks(PkArgs a, PR thr) {
     for (int r = 0; r < TY; r++) {
       // the shuffles run in every lane, whatever the region says
       PR left = __shfl(cur[r].v[V - 1], lane_l, 64), right = __shfl(cur[r].v[0], lane_r, 64);
-      if (!in_l) left = pc[(long long)row[r] + off_l];
-      if (!in_r) right = pc[(long long)row[r] + off_r];
+      if (!in_l) left = through(pc[(long long)row[r] + off_l], lxc, my[MAP ? r + 1 : 0], mz[0]);
+      if (!in_r) right = through(pc[(long long)row[r] + off_r], lxc, my[MAP ? r + 1 : 0], mz[MAP ? V + 1 : 0]);
       const Vec &up = r > 0 ? cur[r > 0 ? r - 1 : 0] : hlo;
       const Vec &dn = r < TY - 1 ? cur[r < TY - 1 ? r + 1 : 0] : hhi;
 #pragma unroll
@@ -162,6 +211,7 @@ __global__ void __launch_bounds__(PF_PEAK_BLOCK) k_peaks(PkArgs a, PR thr) {
 #pragma unroll
     for (int r = 0; r < TY; r++) cur[r] = nxt[r];
     below = below_next;
+    lxc = lxn;
   }
   unsigned long long c0 = cnt, c1 = cntg;
   for (int o = 32; o > 0; o >>= 1) { c0 += __shfl_down(c0, o, 64); c1 += __shfl_down(c1, o, 64); }
@@ -196,19 +246,21 @@ int pf_peak_region_setup(int n, const pf_peak_region *rg, PfPeakParams *p, int *
   return 0;
 }
 
-template <typename PR, int V, bool KEYS>
-static void launch_peaks(const PkArgs &a, double flast, hipStream_t st) {
+template <typename PR, int V, bool KEYS, bool MAP = false, typename Args = PkArgs>
+static void launch_peaks(const Args &a, double flast, hipStream_t st) {
   const long long ncols = (long long)((a.n + PF_PEAK_TY - 1) / PF_PEAK_TY) * (a.n / V);
   const unsigned int gx = (unsigned int)((ncols + PF_PEAK_BLOCK - 1) / PF_PEAK_BLOCK);
   const unsigned int gy = (unsigned int)((a.nxl + a.xchunk - 1) / a.xchunk);
-  hipLaunchKernelGGL((k_peaks<PR, V, KEYS>), dim3(gx, gy), dim3(PF_PEAK_BLOCK), 0, st, a, thr_of(flast, PR()));
+  hipLaunchKernelGGL((k_peaks<PR, V, KEYS, MAP>), dim3(gx, gy), dim3(PF_PEAK_BLOCK), 0, st, a, thr_of(flast, PR()));
 }
 
 // counters[0] += peaks of the region in this slab, counters[1] += the well resolved ones; keys != null: the sort keys of the
 // peaks appended at counters[2] (fp32 products)
 int pf_launch_peaks(int pb, const PfPeakParams &p, hipStream_t st) {
-  if (p.n < 1 || p.n > 2048 || p.nxl < 1 || (p.keys && pb != 4)) return 1;
-  PkArgs a;
+  if (p.n < 1 || p.n > 2048 || p.nxl < 1 || (p.keys && pb != 4) || (p.keys && p.map)) return 1;
+  PkMapArgs a;   // (the instantiations without a map take its PkArgs part)
+  a.map = p.map;
+  for (int d = 0; d < 3; d++) a.mlen[d] = p.mlen[d];
   a.fmax = p.fmax; a.halo_lo = p.halo_lo; a.halo_hi = p.halo_hi;
   a.n = p.n; a.nxl = p.nxl; a.x0 = p.x0;
   for (int d = 0; d < 3; d++) { a.start[d] = p.start[d]; a.lo[d] = p.lo[d]; a.hi[d] = p.hi[d]; a.glo[d] = p.glo[d]; a.ghi[d] = p.ghi[d]; }
@@ -220,7 +272,15 @@ int pf_launch_peaks(int pb, const PfPeakParams &p, hipStream_t st) {
   if (chunks > p.nxl / 8) chunks = p.nxl / 8;
   if (chunks < 1) chunks = 1;
   a.xchunk = (int)((p.nxl + chunks - 1) / chunks);
-  if (pb == 8) {
+  if (p.map) {
+    if (pb == 8) {
+      if (v == 2) launch_peaks<double, 2, false, true>(a, p.flast, st);
+      else launch_peaks<double, 1, false, true>(a, p.flast, st);
+    } else {
+      if (v == 4) launch_peaks<float, 4, false, true>(a, p.flast, st);
+      else launch_peaks<float, 1, false, true>(a, p.flast, st);
+    }
+  } else if (pb == 8) {
     if (v == 2) launch_peaks<double, 2, false>(a, p.flast, st);
     else launch_peaks<double, 1, false>(a, p.flast, st);
   } else if (p.keys) {

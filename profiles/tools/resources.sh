@@ -9,7 +9,7 @@ flags="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=on -DPF_FP_CONTR
 import re, sys
 cur = {}
 for line in sys.stdin:
-    m = re.search(r"remark: .*?: (.*)$", line)
+    m = re.search(r"remark: (?:[^ ]+:\d+:\d+: )?(.*?)(?: \[-Rpass-analysis=kernel-resource-usage\])?$", line)
     if not m: continue
     t = m.group(1).strip()
     if t.startswith("Function Name:"):
