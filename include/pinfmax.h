@@ -436,6 +436,48 @@ int pf_distribute_sorted_map(pf_ctx *ctx, double flast, pf_map *m, int which, co
    for stored.  Region (= the map's box), border skipping, well resolved test, slab halos and sums as pf_count_peaks; collective,
    every rank holding the same words.  peaks[0] is the reference's Npeaks ("found %d peaks") of either turn. */
 int pf_count_peaks_map(pf_ctx *ctx, double flast, pf_map *m, int which, unsigned long long peaks[2]);
+/* The neighbour table of the stored particles: every find_location() (src/fragment.c:592-603) that the loops of count_peaks()
+   (:605-706), quick_build_groups() (src/build_groups.c:1916-2004) and build_groups() (:245-343) issue -- six per particle, each a
+   bsearch over all stored positions followed by indices[pos] and an Fmax comparison -- answered for every particle in one call,
+   with the per-particle flags the loops derive beside them.  None of it depends on the group state; the order-dependent group
+   construction stays on the host and reads the table.
+   The particles are in the order after sort_and_organize(); box = subbox.stabl, subbox.Lgwbl, subbox.safe; positions are
+   pos = z + Lz (y + Ly x) (COORD_TO_INDEX, src/pinocchio.h:84-85).  For particle iz: (i, j, k) = INDEX_TO_COORD(frag_pos[iz]);
+   PF_NEIGH_SKIP when a coordinate is 0 or len - 1 in a direction that is not periodic (src/build_groups.c:251-254); PF_NEIGH_GOOD
+   when safe[d] <= coord < len[d] - safe[d] in all three (good_particle, :262-264); neigh[6 iz + nn], nn = 0..5 = x-, x+, y-, y+,
+   z-, z+ with the single wrap of the switch at :274-306, is the index IN THE SAME ORDER of the particle stored at the neighbour's
+   position -- the reference's indices[find_location(i1, j1, k1)] -- or -1 when none is stored there; all six are -1 for a skipped
+   particle, which the reference never looks up.  PF_NEIGH_PEAK: not skipped and Fmax[iz] > Fmax[neigh] for every neighbour that
+   is present (:322), the C comparison in the product precision: a NaN on either side clears it; a periodic direction of length 1
+   makes a particle its own neighbour and never a peak, one of length 2 gives the same index twice.  peaks[0] counts the PEAK
+   particles (the reference's Npeaks), peaks[1] those that are GOOD too (Ngood); 64-bit, independent of the schedule.
+   pf_neighbours: on arrays the caller holds (the contributions of several ranks after pf_organize).  fmax points at the first
+   particle's Fmax and fmax_stride is the byte distance to the next -- (char *)frag + off_Fmax and sizeof(product_data) --, float,
+   or double for a context with PF_FLAG_DOUBLE_PRODUCTS; the host packs the values while it stages the upload, so 8 (12) bytes per
+   particle go up and nothing else of the records.  The position index is built on the device by the call itself; equal positions
+   give one of the duplicates.  ctx may be NULL (current device, default stream, float Fmax, a direction periodic when
+   safe[d] == 0); with a context a direction is periodic when len[d] == n.  The box is checked as pf_map_create checks it.  neigh
+   and flags may each be NULL (both: a count).  count = 0 gives peaks = {0, 0}.  Not collective.
+   pf_distribute_sorted_neighbours_map = pf_distribute_sorted_map plus the table of exactly the records it returns -- the first
+   min(*count, capacity) of the sorted order; a neighbour beyond the capacity is absent -- without a second trip: box and safe are
+   the map's, the first four arrays and *count are byte for byte those of pf_distribute_sorted_map, every output may be NULL.
+   Refused, with nothing written and no kernel launched: 2^31 records or more (the table is int like indices[]); a frag_pos entry
+   that is not below Lx Ly Lz (checked on the host while staging: every index on the device is then in range whatever the caller
+   passes); a stride that is no multiple of the element size; a map of another context.  When the scratch cannot be allocated the
+   call says how many bytes it needs.  Results leave through the hand-off pieces (PF_HANDOFF_CHUNK_MB).  PF_NEIGH_ROWS=0, read
+   per call, selects the plain form of the kernel (one search of the whole of sorted_pos per neighbour; A/B, same results). */
+#define PF_NEIGH_SKIP 1
+#define PF_NEIGH_GOOD 2
+#define PF_NEIGH_PEAK 4
+int pf_neighbours(pf_ctx *ctx, const pf_peak_region *box, size_t count, const unsigned int *frag_pos, const void *fmax,
+                  size_t fmax_stride, int *neigh /* [6 * count] */, unsigned char *flags /* [count] */, unsigned long long peaks[2]);
+int pf_distribute_sorted_neighbours_map(pf_ctx *ctx, double flast, pf_map *m, int which, const pf_product_layout *layout,
+                                        size_t capacity, void *frag, unsigned int *frag_pos, unsigned int *sorted_pos, int *indices,
+                                        int *neigh, unsigned char *flags, unsigned long long peaks[2], size_t *count);
+/* measurement aid (profiles/tools/neigh_time.py): device time in ms of the position sort and of the table kernels (Fmax gather, row
+   starts, lookups) of the calling thread's last context-free pf_neighbours that ran under PF_NEIGH_STATS=1 (read per call: such a
+   call brackets the two parts with HIP events; the default records nothing and the call refuses) */
+int pf_debug_neigh_ms(double *sort_ms, double *table_ms);
 /* Per-particle payload of one block of the "timeless snapshot" (write_timeless_snapshot, src/write_snapshot.c:207-342)
    for this rank's slab, from the SoA columns in HBM: name = "ID  " (1 + global index as MYIDTYPE of id_bytes = 4 or 8,
    :648-664), "FMAX" float, "RMAX" int, "ZEL " / "2LPT" / "31PT" / "32PT" float[3] per particle (:700-855). */

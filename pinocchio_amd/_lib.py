@@ -18,6 +18,7 @@ FLAG_TIMING = 1
 FLAG_DOUBLE_PRODUCTS = 2
 MAP_CURRENT = 0   # frag_map
 MAP_UPDATE = 1    # frag_map_update
+NEIGH_SKIP, NEIGH_GOOD, NEIGH_PEAK = 1, 2, 4   # PF_NEIGH_*: the flags of the neighbour table
 
 
 class Config(C.Structure):
@@ -126,6 +127,12 @@ PROTOTYPES = {
     "pf_distribute_sorted_map": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.POINTER(ProductLayout), C.c_size_t, _vp, C.POINTER(C.c_uint),
                                            C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "pf_count_peaks_map": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "pf_neighbours": (C.c_int, [_vp, C.POINTER(PeakRegion), C.c_size_t, C.POINTER(C.c_uint), _vp, C.c_size_t, C.POINTER(C.c_int),
+                                C.POINTER(C.c_ubyte), C.POINTER(C.c_ulonglong)]),
+    "pf_debug_neigh_ms": (C.c_int, [_dp, _dp]),
+    "pf_distribute_sorted_neighbours_map": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.POINTER(ProductLayout), C.c_size_t, _vp, C.POINTER(C.c_uint),
+                                                      C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ubyte),
+                                                      C.POINTER(C.c_ulonglong), C.POINTER(C.c_size_t)]),
     "pf_set_collapse_model": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "pf_set_modified_gravity": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "pf_set_tabulated_ct": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),

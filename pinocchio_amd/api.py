@@ -127,6 +127,35 @@ def debug_organize(fmax: np.ndarray, frag_pos: np.ndarray):
     return order, spos, ind
 
 
+def _neighbours(L, ctx, frag_pos, fmax, start, length, safe, ftype):
+    pos = np.ascontiguousarray(frag_pos, dtype=np.uint32).ravel()
+    f = np.asarray(fmax)
+    if f.dtype != ftype:
+        f = f.astype(ftype)
+    if f.ndim != 1 or f.size != pos.size:
+        raise ValueError(f"Fmax of shape {f.shape} for {pos.size} positions")
+    if pos.size > 1 and f.strides[0] <= 0:
+        f = np.ascontiguousarray(f)
+    stride = f.strides[0] if pos.size > 1 else f.dtype.itemsize     # a field of a structured array: the stride of its records
+    rg = _region((start, length, safe))
+    neigh = np.empty((pos.size, 6), dtype=np.int32)
+    flags = np.empty(pos.size, dtype=np.uint8)
+    peaks = (C.c_ulonglong * 2)()
+    if L.pf_neighbours(ctx, C.byref(rg), pos.size, pos.ctypes.data_as(C.POINTER(C.c_uint)), C.c_void_p(f.ctypes.data), stride,
+                       neigh.ctypes.data_as(C.POINTER(C.c_int)), flags.ctypes.data_as(C.POINTER(C.c_ubyte)), peaks):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_neighbours failed")
+    return neigh, flags, (int(peaks[0]), int(peaks[1]))
+
+
+def neighbours(frag_pos, fmax, start, length, safe):
+    """The neighbour table of stored particles in the order after sort_and_organize (pf_neighbours without a context: fp32 Fmax, a
+    direction periodic when safe == 0) -> (neigh[count, 6], flags[count], (npeaks, ngood)).  neigh[iz, nn], nn = x-, x+, y-, y+, z-,
+    z+: the index of the particle stored at that neighbour of frag_pos[iz] in the box (start, length, safe), -1 when none is (what
+    the reference computes as indices[find_location(i1, j1, k1)], src/build_groups.c:274-323); flags: _lib.NEIGH_SKIP / NEIGH_GOOD /
+    NEIGH_PEAK.  fmax may be a strided view (the Fmax field of a record array): only the values are uploaded."""
+    return _neighbours(_lib.load(), None, frag_pos, fmax, start, length, safe, np.float32)
+
+
 _WHICH = {"current": _lib.MAP_CURRENT, "update": _lib.MAP_UPDATE}
 
 
@@ -543,6 +572,44 @@ class Fmax:
         if dtype is not None:
             rec = rec.view(dtype).reshape(m)
         return rec, pos[:m], spos[:m], ind[:m], int(cnt.value)
+
+    def distribute_sorted_neighbours(self, flast: float, map: FragMap, which="current", layout=None, capacity=None):
+        """distribute_sorted() over the box of a FragMap of this context plus the neighbour table of the records it returns, in one
+        call (pf_distribute_sorted_neighbours_map) -> (records, frag_pos, sorted_pos, indices, neigh[count, 6], flags, (npeaks,
+        ngood), count).  The first four and count are those of distribute_sorted(); neigh / flags / peaks as neighbours(), for the
+        box and safety layers of the map; with a capacity below the count they describe the returned records only.  Not collective."""
+        dtype = None
+        if layout is None:
+            layout, dtype = self.product_layout()
+        self._own_map(map)
+        cnt = C.c_size_t()
+        peaks = (C.c_ulonglong * 2)()
+
+        def call(cap, rec, pos, spos, ind, nb, fl, pk):
+            return self.L.pf_distribute_sorted_neighbours_map(self.h, float(flast), map.h, _which(which), C.byref(layout), cap, rec, pos, spos, ind,
+                                                              nb, fl, pk, C.byref(cnt))
+        if capacity is None:
+            self._chk(call(0, None, None, None, None, None, None, None))
+            capacity = cnt.value
+        capacity = int(capacity)
+        rec = np.zeros((capacity, layout.stride), dtype=np.uint8)
+        pos = np.empty(capacity, dtype=np.uint32)
+        spos = np.empty(capacity, dtype=np.uint32)
+        ind = np.empty(capacity, dtype=np.int32)
+        neigh = np.empty((capacity, 6), dtype=np.int32)
+        flags = np.empty(capacity, dtype=np.uint8)
+        self._chk(call(capacity, rec.ctypes.data_as(C.c_void_p), pos.ctypes.data_as(C.POINTER(C.c_uint)), spos.ctypes.data_as(C.POINTER(C.c_uint)),
+                       ind.ctypes.data_as(C.POINTER(C.c_int)), neigh.ctypes.data_as(C.POINTER(C.c_int)), flags.ctypes.data_as(C.POINTER(C.c_ubyte)), peaks))
+        m = min(cnt.value, capacity)
+        rec = rec[:m]
+        if dtype is not None:
+            rec = rec.view(dtype).reshape(m)
+        return rec, pos[:m], spos[:m], ind[:m], neigh[:m], flags[:m], (int(peaks[0]), int(peaks[1])), int(cnt.value)
+
+    def neighbours(self, frag_pos, fmax, start, length, safe):
+        """neighbours() with this context: Fmax of the context's product precision, a direction periodic when length == n, the
+        transfers through the hand-off pieces (pf_neighbours)"""
+        return _neighbours(self.L, self.h, frag_pos, fmax, start, length, safe, np.float64 if self.double_products else np.float32)
 
     def organize(self, records: np.ndarray, frag_pos: np.ndarray, layout=None):
         """sort_and_organize() (src/fragment.c:484-520) on records the caller holds (contributions of several ranks to one

@@ -22,6 +22,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <string>
 #include <functional>
 #include <vector>
@@ -2228,6 +2229,37 @@ void pf_ctx_host_copy(pf_ctx *c, void *dst, const void *src, size_t bytes) {
 }
 int pf_ctx_d2h(pf_ctx *c, void *host, const void *src_dev, size_t bytes) { return handoff_d2h(c, (char *)host, (const char *)src_dev, bytes, 4, no_fill); }
 int pf_ctx_h2d(pf_ctx *c, void *dst_dev, const void *host, size_t bytes) { return handoff_h2d(c, (char *)dst_dev, (const char *)host, bytes); }
+int pf_ctx_h2d_packed(pf_ctx *c, void *dst_dev, const void *host, size_t count, size_t elem, size_t stride, unsigned long long limit, size_t *bad) {
+  PfHandoff *h;
+  if (handoff_get(c, &h)) return 1;
+  PFCHK(c, handoff_begin(c, h));
+  const size_t per = h->chunk / elem, np = (count + per - 1) / per;
+  std::atomic<size_t> first_bad(~(size_t)0);
+  for (size_t k = 0; k < np; k++) {
+    const int b = (int)(k & 1);
+    const size_t first = k * per, cnt = count - first < per ? count - first : per;
+    HIPCHK(c, hipStreamSynchronize(h->st[b]));  // the DMA that last read this buffer (piece k - 2)
+    char *dst = h->pin[b]; const char *src = (const char *)host + first * stride;
+    h->pool->run(cnt, [&, dst, src](size_t a, size_t e) {
+      if (stride == elem) memcpy(dst + a * elem, src + a * elem, (e - a) * elem);
+      else for (size_t i = a; i < e; i++) memcpy(dst + i * elem, src + i * stride, elem);
+      if (limit)
+        for (size_t i = a; i < e; i++) {
+          unsigned int p;
+          memcpy(&p, dst + i * elem, sizeof(p));
+          if (p >= limit) { first_bad.store(first + i); break; }
+        }
+    });
+    if (first_bad.load() != ~(size_t)0) {
+      for (int i = 0; i < 2; i++) HIPCHK(c, hipStreamSynchronize(h->st[i]));
+      *bad = first_bad.load();
+      return 2;
+    }
+    HIPCHK(c, hipMemcpyAsync((char *)dst_dev + first * elem, h->pin[b], cnt * elem, hipMemcpyHostToDevice, h->st[b]));
+  }
+  for (int i = 0; i < 2; i++) HIPCHK(c, hipStreamSynchronize(h->st[i]));
+  return 0;
+}
 void *pf_ctx_timer_begin(pf_ctx *c, int phase, double bytes, hipStream_t st) {
   return phase ? (void *)new PhaseTimer(c, 3, st) : (void *)new KTimer(c, KS_DISTRIBUTE, bytes, st);
 }

@@ -301,10 +301,28 @@ struct PfScopedTimer {
 struct PfMapView { int start[3], len[3], safe[3]; const unsigned int *bits; size_t words; };
 // refuses (message of `who`) a null map, a map of another context and a `which` that names no array
 int pf_map_view(const char *who, pf_ctx *c, int rank, pf_map *m, int which, PfMapView *v);
-// pf_distribute_sorted with the map on the host or (map_host null) on the device (pf_organize.hip)
+// the box check of pf_map_create (len, safe, periodic directions, 2^32 cells; n = 0 without a context), shared with pf_neighbours
+struct PfMapBox;
+int pf_map_box_check(const char *who, int rank, int n, const pf_peak_region *box, PfMapBox *mb, unsigned long long *cells);
+// ---- pf_neighbours.hip: the neighbour table of the stored particles ----
+// what the fused call asks of pf_distribute_sorted_impl beside its own outputs (host pointers, each may be null)
+struct PfNeighOut { int len[3], pbc[3], safe[3]; bool rows; int *neigh; unsigned char *flags; unsigned long long *peaks; };
+// the table of the first m records of the sorted order from the position index that lies on the device; Fmax of record i is element
+// cell[perm[i]] of the column fmax (pb bytes each).  Results through the hand-off pieces of the context
+int pf_neigh_from_index(pf_ctx *c, const PfCtxView &v, const char *who, const PfNeighOut &nb, size_t m, const unsigned int *sorted_pos,
+                        const unsigned int *indices, const unsigned int *perm, const unsigned int *cell, const void *fmax);
+// the position sort of pf_organize.hip on its own: m positions in k0 -> *sorted_pos / *indices (each one of the four buffers of m
+// words); *tmp is rocPRIM's, the caller's to free once the stream has drained
+int pf_org_position_sort(unsigned int *k0, unsigned int *k1, unsigned int *v0, unsigned int *v1, size_t m, unsigned int pos_bits, void **tmp,
+                         hipStream_t st, unsigned int **sorted_pos, unsigned int **indices);
+// `count` elements of `elem` bytes that lie `stride` bytes apart in the caller's memory, packed by the host threads while they fill
+// the pinned pieces, to dst_dev.  limit != 0: the elements are 32-bit positions, and one that is not below limit ends the upload:
+// 2 is returned (no message) and *bad is the index of one such element
+int pf_ctx_h2d_packed(pf_ctx *c, void *dst_dev, const void *host, size_t count, size_t elem, size_t stride, unsigned long long limit, size_t *bad);
+// pf_distribute_sorted with the map on the host or (map_host null) on the device (pf_organize.hip); nb: the neighbour table too
 int pf_distribute_sorted_impl(const char *who, pf_ctx *c, double flast, const pf_subbox *sub, const unsigned int *map_host, const unsigned int *map_dev,
                               const pf_product_layout *l, size_t capacity, void *frag, unsigned int *frag_pos, unsigned int *sorted_pos, int *indices,
-                              size_t *count);
+                              size_t *count, const PfNeighOut *nb = nullptr);
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);

@@ -175,13 +175,8 @@ int pf_map_view(const char *who, pf_ctx *c, int rank, pf_map *m, int which, PfMa
   return 0;
 }
 
-// -------------------------------------------------------------------------------------------------------- entry points ----
-extern "C" int pf_map_create(pf_ctx *c, const pf_peak_region *box, pf_map **out) {
-  const char *who = "pf_map_create";
-  int rank = 0, n = 0;
-  if (c) { PfCtxView v; pf_ctx_view(c, &v); rank = v.rank; n = v.n; }
-  if (!box || !out) return pf_fail(rank, "%s: null argument", who);
-  *out = nullptr;
+// the box of a map, and of the neighbour table (pf_neighbours.hip): n = 0 without a context
+int pf_map_box_check(const char *who, int rank, int n, const pf_peak_region *box, PfMapBox *out, unsigned long long *ncells) {
   const int nmax = n ? n : 2048;
   unsigned long long cells = 1;
   PfMapBox mb;
@@ -197,6 +192,20 @@ extern "C" int pf_map_create(pf_ctx *c, const pf_peak_region *box, pf_map **out)
     cells *= (unsigned long long)len;
   }
   if (cells > (1ull << 32)) return pf_fail(rank, "%s: a sub-box of more than 2^32 cells (bit positions are 32-bit as in the reference)", who);
+  *out = mb; *ncells = cells;
+  return 0;
+}
+
+// -------------------------------------------------------------------------------------------------------- entry points ----
+extern "C" int pf_map_create(pf_ctx *c, const pf_peak_region *box, pf_map **out) {
+  const char *who = "pf_map_create";
+  int rank = 0, n = 0;
+  if (c) { PfCtxView v; pf_ctx_view(c, &v); rank = v.rank; n = v.n; }
+  if (!box || !out) return pf_fail(rank, "%s: null argument", who);
+  *out = nullptr;
+  unsigned long long cells = 1;
+  PfMapBox mb;
+  if (pf_map_box_check(who, rank, n, box, &mb, &cells)) return 1;
   pf_map *m = new pf_map();
   m->ctx = c; m->rank = rank; m->n = n; m->box = *box; m->mb = mb; m->cells = cells; m->words = (size_t)((cells + 31) / 32);
   m->bits[0] = m->bits[1] = nullptr; m->counters = nullptr; m->atomics = 0; m->dgroups = nullptr; m->dprefix = nullptr; m->dcap = 0;

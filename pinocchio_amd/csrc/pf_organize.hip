@@ -310,9 +310,22 @@ static unsigned int bits_for(unsigned long long cells) {   // positions lie belo
   return b;
 }
 
+// the position sort alone, for positions the caller has put on the device (pf_neighbours.hip)
+int pf_org_position_sort(unsigned int *k0, unsigned int *k1, unsigned int *v0, unsigned int *v1, size_t m, unsigned int pos_bits, void **tmp,
+                         hipStream_t st, unsigned int **sorted_pos, unsigned int **indices) {
+  PfOrgScratch o;
+  memset(&o, 0, sizeof(o));
+  unsigned int *other;
+  hipLaunchKernelGGL(k_org_iota, dim3(org_grid(m)), dim3(PF_ORG_BLOCK), 0, st, m, v0);
+  if (hipGetLastError() != hipSuccess) return 1;
+  const int rc = org_sort_pairs(k0, k1, v0, v1, m, pos_bits, &o, st, sorted_pos, indices, &other);
+  *tmp = o.tmp;
+  return rc;
+}
+
 int pf_distribute_sorted_impl(const char *who, pf_ctx *c, double flast, const pf_subbox *sub, const unsigned int *map, const unsigned int *map_dev,
                               const pf_product_layout *l, size_t capacity, void *frag, unsigned int *frag_pos, unsigned int *sorted_pos, int *indices,
-                              size_t *count) {
+                              size_t *count, const PfNeighOut *nb) {
   if (!c) return pf_fail(0, "%s: null argument", who);
   PfCtxView v;
   pf_ctx_view(c, &v);
@@ -343,8 +356,10 @@ int pf_distribute_sorted_impl(const char *who, pf_ctx *c, double flast, const pf
   if (total > 0x7FFFFFFFull)
     return pf_fail(v.rank, "%s: %llu records in one sub-box: indices[] is int as in the reference, 2^31 - 1 records at most", who, total);
   const size_t m = *count < capacity ? *count : capacity;
-  if (!m || (!frag && !frag_pos && !sorted_pos && !indices)) return 0;
-  const bool index = sorted_pos || indices;
+  const bool table = nb && (nb->neigh || nb->flags || nb->peaks);
+  if (!m && nb && nb->peaks) nb->peaks[0] = nb->peaks[1] = 0;
+  if (!m || (!frag && !frag_pos && !sorted_pos && !indices && !table)) return 0;
+  const bool index = sorted_pos || indices || table;
   PfOrgScratch o;
   memset(&o, 0, sizeof(o));
   OrgGuard guard{&o};
@@ -362,6 +377,7 @@ int pf_distribute_sorted_impl(const char *who, pf_ctx *c, double flast, const pf
       return pf_fail(v.rank, "%s: sort failed (out of memory?)", who);
   }
   if (index && org_index_leave(c, v, who, in, m, bits_for((unsigned long long)t.slen[0] * t.slen[1] * t.slen[2]), &o, sorted_pos, indices)) return 1;
+  if (table && pf_neigh_from_index(c, v, who, *nb, m, o.sorted_pos, o.indices, o.perm, o.cell, v.fmax)) return 1;
   if (!frag && !frag_pos) { ORGHIP(v.rank, who, hipStreamSynchronize(v.stream)); return 0; }
   return org_leave(c, v, who, in, o.perm, rec, stride, m, frag, frag_pos, v.distribute_lds);
 }
