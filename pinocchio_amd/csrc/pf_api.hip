@@ -187,6 +187,12 @@ struct pf_ctx {
   // pf_set_sources_in_sweep: the solve of a sweep's last radius also writes the LPT sources (S[0..2], real space) and the
   // sum of S2; sources_fresh says they are what pf_displacements(1, 0) would compute from the Hessian in B
   bool sweep_sources, sources_fresh;
+  // PF_LPT_XFUSE, one rank: the spectrum in S[i] has been transformed along z and y only; its x-transform is done by every inverse
+  // x-pass that reads it (k_strided with PF_DIR_XF), or in place by finish_forward_x where the whole spectrum is wanted (pf_get_kvector)
+  bool x_pending[3];
+  // the solve of the sweep's last radius has left S[2] unwritten: the z-pass that contracts the second-order Hessian into it forms the
+  // start value 2 (h11 + h22 + h33) S2 itself (lpt3b_start_in_zpass; meaningful while sources_fresh)
+  bool s3b_start_absent;
   bool transposed; // spectra cross the boundary as [ky_local][kx][kz] (pf_set_transposed_spectra)
   int ct_flavour; // table interpolation of the build: 0 BILINEAR_SPLINE, 1 TRILINEAR, 2 ALL_SPLINE (pf_set_ct_interpolation)
   int lpt_order;  // 3: -DTWO_LPT -DTHREE_LPT (default), 2: -DTWO_LPT only, 1: Zel'dovich only (pf_set_lpt_order)
@@ -334,6 +340,8 @@ static void read_tuning(PfTuning *t) {
   t->exact_libm = env_int("PF_EXACT_LIBM", 0) != 0;
   t->solve_beside_z = env_int("PF_SOLVE_BESIDE_Z", -1);
   t->gtab = env_int("PF_GTAB", 1) != 0;
+  t->lpt_xfuse = env_int("PF_LPT_XFUSE", 1) != 0;
+  t->lpt3b_start = env_int("PF_LPT3B_START", 0) != 0;
   t->preflight = env_int("PF_PREFLIGHT", 1) != 0;
   t->handoff_chunk_mb = env_int("PF_HANDOFF_CHUNK_MB", 256);
   if (t->handoff_chunk_mb <= 0) t->handoff_chunk_mb = 256;
@@ -511,7 +519,7 @@ extern "C" int pf_create(pf_ctx **out, const pf_config *cfg) {
   c->dev_bytes = 0; c->own_stream = true; c->stream = nullptr;
   c->a2a = nullptr; c->a2av = nullptr; c->a2av_user = nullptr; c->ared = nullptr; c->a2a_user = c->ared_user = nullptr; c->rccl = nullptr;
   c->have_density = c->have_hessian = c->have_sources = c->products_init = false; c->last_ns = 0;
-  c->sweep_sources = c->sources_fresh = false; c->partials_src = nullptr; c->lpt_order = 3; c->ct_flavour = 0; c->transposed = false;
+  c->sweep_sources = c->sources_fresh = false; c->x_pending[0] = c->x_pending[1] = c->x_pending[2] = false; c->s3b_start_absent = false; c->partials_src = nullptr; c->lpt_order = 3; c->ct_flavour = 0; c->transposed = false;
   c->vel_zero_pending = false; c->have_genic = false;
   memset(c->ks_ms, 0, sizeof(c->ks_ms)); memset(c->ks_bytes, 0, sizeof(c->ks_bytes)); memset(c->ks_n, 0, sizeof(c->ks_n));
   memset(&c->cpu, 0, sizeof(c->cpu)); memset(c->spl_set, 0, sizeof(c->spl_set)); memset(c->spl_n, 0, sizeof(c->spl_n));
@@ -807,8 +815,9 @@ static PfAddr addr_xs_y(const pf_ctx *c) {  // XS layout, e = y, outer = x_local
 
 struct Job { const void *in; void *out; int mul; };
 
+// fwd_first: the (single) input still lacks its forward x-transform (x_pending): the pass does it on each tile it loads
 static int xpass(pf_ctx *c, int kind, int dir, int njobs, const Job *jobs, int pre, double rs, double growth, int nin, int band = 1 << 30,
-                 bool out_yblocks = false, bool replicated = false) {
+                 bool out_yblocks = false, bool replicated = false, bool fwd_first = false) {
   PfStridedParams p; memset(&p, 0, sizeof(p));
   p.njobs = njobs;
   for (int j = 0; j < njobs; j++) { p.job[j].in = jobs[j].in; p.job[j].out = jobs[j].out; p.job[j].mul = jobs[j].mul; }
@@ -830,6 +839,11 @@ static int xpass(pf_ctx *c, int kind, int dir, int njobs, const Job *jobs, int p
   }
   // (replicated: the whole spectrum is read, P slabs; one slab per output is written)
   KTimer t(c, kind, (nin * frac_in * (replicated ? c->P : 1) + njobs) * frac_cols * frac_outer * spec_bytes_alg(c));
+  if (fwd_first) {
+    if (dir < 0 || replicated) return pf_fail(c->rank, "xpass: a pending forward x-transform goes with an inverse pass over this rank's own spectrum");
+    PFCHK(c, pf_launch_strided_xfuse(c->fb, c->n, p, c->stream));
+    return 0;
+  }
   PFCHK(c, pf_launch_strided(c->fb, c->n, dir, p, c->stream));
   return 0;
 }
@@ -873,8 +887,10 @@ static int zpass_c2r(pf_ctx *c, int kind, int njobs, const ZJob *jobs, const dou
   p.flag = c->scal + SC_INV_FLAG;
   if (acc) {  // six components in, none out: acc -= 2 phi2_ab h_ab with the first-order Hessian h in jobs[].out (src/LPT.c:134-137)
     p.acc = acc;
-    KTimer t(c, KS_ZPASS_LPT3B, njobs * frac_in * spec_bytes_alg(c) + 8.0 * real_bytes_alg(c));
-    PFCHK(c, pf_launch_c2r_invariants(c->fb, c->n, p, c->stream, 1));
+    const bool start_here = c->s3b_start_absent;  // acc is written only: one field less
+    KTimer t(c, KS_ZPASS_LPT3B, njobs * frac_in * spec_bytes_alg(c) + (start_here ? 7.0 : 8.0) * real_bytes_alg(c));
+    PFCHK(c, pf_launch_c2r_invariants(c->fb, c->n, p, c->stream, start_here ? 2 : 1));
+    c->s3b_start_absent = false;
     return 0;
   }
   if (invariants) {  // six components in, the three invariants of the tensor out (fields 0..2; fp32 fields: fp64 rows in INV)
@@ -1014,6 +1030,17 @@ static int g_reverse_of(pf_ctx *c, void *f) {
   return g_c2r(c, c->W, f);
 }
 
+// the contraction into the 3LPT(b) source runs inside the z-pass of the second-order Hessian (k_c2r_invariants, MODE 1 / 2)
+static bool lpt3b_in_zpass(const pf_ctx *c) {
+  return (c->tune.lpt_fuse >= 2 ? pf_c2r_invariants_supported(c->fb, (int)c->n) : pf_c2r_invariants_preferred(c->fb, (int)c->n)) && !c->general && c->tune.lpt_fuse;
+}
+// ... and forms the source's start value too, so that the solve of the sweep's last radius need not store it (one rank, the
+// power-of-two z-pass; PF_LPT3B_START=1: the field is written and read as before).  One predicate for the sweep, which leaves the
+// store out, and for pf_displacements, which must then pick MODE 2: the outcome travels in s3b_start_absent.
+static bool lpt3b_start_in_zpass(const pf_ctx *c) {
+  return lpt3b_in_zpass(c) && !c->tune.lpt3b_start && c->sweep_sources && c->lpt_order >= 3 && c->P == 1 && !(c->n & (c->n - 1));
+}
+
 // six second derivatives of `spec` (KY layout) at smoothing rs -> six real fields out[0..5] (R layout)
 // order 11,22,33,12,13,23 (src/LPT.c:36-44); compute_second_derivatives, src/fmax.c:225-258
 // Gaussian window exp(-k^2 rs^2/2) < prune_eps (2^-60) beyond |k| = sqrt(-2 ln eps)/rs: those modes are dropped
@@ -1027,9 +1054,23 @@ static int hess_band(const pf_ctx *c, double rs) {
   }
   return band;
 }
+// index of the LPT source field whose spectrum `spec` is and whose forward x-transform is still pending, or -1
+static int x_pending_of(const pf_ctx *c, const void *spec) {
+  for (int i = 0; i < 3; i++) if (c->x_pending[i] && spec == c->S[i]) return i;
+  return -1;
+}
+// the plain forward x-pass of forward_many on a pending field, in place: from here on S[i] is the whole spectrum
+static int finish_forward_x(pf_ctx *c, int i) {
+  const Job xj[1] = {{c->S[i], c->S[i], PF_MUL_ONE}};
+  PFCHK(c, xpass(c, KS_XPASS_FWD, -1, 1, xj, 0, 0.0, 1.0, 1));
+  c->x_pending[i] = false;
+  return 0;
+}
 static int hess_x(pf_ctx *c, const void *spec, double rs, void *const A[3], int band, bool replicated = false) {
   const Job xj[3] = {{spec, A[0], PF_MUL_ONE}, {spec, A[1], PF_MUL_K}, {spec, A[2], PF_MUL_K2}};
-  return xpass(c, KS_XPASS_HESS, +1, 3, xj, 1, rs, 1.0, 1, band, true, replicated);
+  int pend = replicated ? -1 : x_pending_of(c, spec);
+  if (pend >= 0 && band < c->n / 2) { PFCHK(c, finish_forward_x(c, pend)); pend = -1; }  // (a band limit masks the loads of the inverse pass: not a case of the fused kernel)
+  return xpass(c, KS_XPASS_HESS, +1, 3, xj, 1, rs, 1.0, 1, band, true, replicated, pend >= 0);
 }
 // gathers delta(k) of all ranks into dk_full, once per density: this rank's ky-slab goes to its place in a zeroed array
 // and an integer all-reduce adds the other ranks' zeros to it (exact for either field type; ~2 x 8.6 GB per rank at 1024^3)
@@ -1100,6 +1141,8 @@ static int displacements_of(pf_ctx *c, int count, const void *const *specs, cons
                      const int o = ord[j];
                      const void *spec = rep ? c->dk_full : sp[j];
                      double growth = c->growth[o];
+                     int pend = rep ? -1 : x_pending_of(c, spec);
+                     if (pend >= 0 && c->gt_n[o]) { PFCHK(c, finish_forward_x(c, pend)); pend = -1; }  // k_apply_growth reads the whole spectrum
                      if (c->gt_n[o]) {
                        KTimer t(c, KS_MISC, 2.0 * spec_bytes_alg(c));
                        PFCHK(c, pf_launch_apply_growth(c->fb, spec, A[2], c->n, c->nyl, c->nzh, c->nzp, c->rank * c->nyl, c->gtab + o * PF_KBIN_CAP,
@@ -1108,7 +1151,7 @@ static int displacements_of(pf_ctx *c, int count, const void *const *specs, cons
                        growth = 1.0;
                      }
                      const Job xj[2] = {{spec, A[0], PF_MUL_ONE}, {spec, A[1], PF_MUL_IK}};
-                     return xpass(c, KS_XPASS_DISP, +1, 2, xj, 1, 0.0, growth, 1, 1 << 30, true, rep);
+                     return xpass(c, KS_XPASS_DISP, +1, 2, xj, 1, 0.0, growth, 1, 1 << 30, true, rep, pend >= 0);
                    },
                    [&](int, int set, int f) { return recv_field(c, set, f); },
                    [&](int j, const void *const *R) {
@@ -1157,6 +1200,11 @@ static int forward_many(pf_ctx *c, int count, void *const *fs) {
       PFCHK(c, forward_r2c(c, f));
       const Job yj[1] = {{f, f, PF_MUL_ONE}};
       PFCHK(c, ypass(c, KS_YPASS_FWD, -1, 1, yj, false, false, 1));
+      // an LPT source: its x-transform is left to the inverse x-passes that read it (hess_x, displacements_of)
+      int si = -1;
+      for (int k = 0; k < 3; k++) if (f == c->S[k]) si = k;
+      if (si >= 0) c->x_pending[si] = c->tune.lpt_xfuse && pf_strided_xfuse_supported(c->fb, (int)c->n);
+      if (si >= 0 && c->x_pending[si]) continue;
       const Job xj[1] = {{f, f, PF_MUL_ONE}};
       PFCHK(c, xpass(c, KS_XPASS_FWD, -1, 1, xj, 0, 0.0, 1.0, 1));
     }
@@ -1500,10 +1548,12 @@ static int collapse_enqueue(pf_ctx *c, int ismooth, void *const H[6], hipStream_
   if (sources) {  // K7 in the same pass (the grid is k_lpt_sources' own: identical partial sums of S2)
     p.sources = 1; p.src[0] = c->S[0]; p.src[1] = c->S[1]; p.src[2] = c->S[2]; p.src_partials = c->partials_src;
     c->have_sources = false;  // S now holds real-space sources, not the resident LPT spectra
+    c->s3b_start_absent = lpt3b_start_in_zpass(c);
+    if (c->s3b_start_absent) p.src[2] = nullptr;
   }
   {
     KTimer t(c, sources ? KS_COLLAPSE_SRC : invariants ? KS_COLLAPSE_INV : KS_COLLAPSE,
-             (double)ncell(c) * ((invariants ? 3.0 * 8.0 / c->fb : sources ? 9.0 : 6.0) * c->fb + 16.0), st);
+             (double)ncell(c) * ((invariants ? 3.0 * 8.0 / c->fb : sources ? (p.src[2] ? 9.0 : 8.0) : 6.0) * c->fb + 16.0), st);
     PFCHK(c, pf_launch_collapse(solve_fb, p, st));
   }
   PFCHK(c, pf_launch_final_sum(c->partials, p.nblocks, c->scal + SC_VAR0 + 2 * ismooth, st));
@@ -1737,7 +1787,8 @@ extern "C" int pf_displacements(pf_ctx *c, int compute_sources, int recompute_sd
     PhaseTimer pt(c, 2);
     if (compute_sources && c->lpt_order >= 2) {  // src/LPT.c:46-175 (#ifdef TWO_LPT)
       if (!c->have_hessian) return pf_fail(c->rank, "pf_displacements: second derivatives at R=0 not in place");
-      if (!c->sources_fresh) {  // (else: the sweep's last solve has left S2, S3a, the S3b start and the sum of S2)
+      if (!c->sources_fresh) {  // (else: the sweep's last solve has left S2, S3a, the S3b start -- unless s3b_start_absent -- and the sum of S2)
+      c->s3b_start_absent = false;  // k_lpt_sources writes all three
       PfLptSrcParams sp; memset(&sp, 0, sizeof(sp));
       for (int i = 0; i < 6; i++) sp.h[i] = c->B[i];
       sp.s2 = c->S[0]; sp.s3a = c->S[1]; sp.s3b = c->S[2]; sp.pitch = rpitch(c); sp.nrows = (long long)c->nxl * c->n; sp.n = c->n;
@@ -1757,7 +1808,9 @@ extern "C" int pf_displacements(pf_ctx *c, int compute_sources, int recompute_sd
       // Hessian of the 2LPT potential contracted with the first-order one into the 3LPT(b) source (src/LPT.c:112-137).  fp64
       // fields: the z-pass does the contraction while it holds a row's six components (nothing of that Hessian is stored;
       // PF_LPT_FUSE=0: six fields out, then k_lpt_accum); same operations per cell either way
-      const bool fuse3b = (c->tune.lpt_fuse >= 2 ? pf_c2r_invariants_supported(c->fb, (int)c->n) : pf_c2r_invariants_preferred(c->fb, (int)c->n)) && !c->general && c->tune.lpt_fuse;
+      const bool fuse3b = lpt3b_in_zpass(c);
+      if (c->lpt_order < 3) c->s3b_start_absent = false;  // (the order was lowered after the sweep: nobody reads S[2])
+      if (c->s3b_start_absent && !fuse3b) return pf_fail(c->rank, "pf_displacements: the sweep left the 3LPT(b) start value to a z-pass that does not run");
       if (c->lpt_order < 3) {  // no THREE_LPT (src/LPT.c:78-92, 113-175): the 2LPT source alone
       } else if (fuse3b) {
         PFCHK(c, hessian_of(c, c->S[0], 0.0, c->scal + SC_DC_S2, c->B2, c->S[2], c->B));
@@ -2301,6 +2354,7 @@ extern "C" int pf_get_second_derivative(pf_ctx *c, int i, double *host) {
 extern "C" int pf_get_kvector(pf_ctx *c, int which, double *host) {
   if (!c || !host || which < 0 || which > 2) return pf_fail(0, "pf_get_kvector: bad argument");
   if (!c->have_sources) return pf_fail(c->rank, "pf_get_kvector: LPT sources not computed");
+  if (c->x_pending[which]) PFCHK(c, finish_forward_x(c, which));  // later passes over this field are the plain ones
   return export_spec(c, c->S[which], host);
 }
 // test tap: rows kx0 .. kx0 + nkx - 1 of the replicated spectrum this rank transforms, [nkx][n (ky)][n/2+1] complex fp64 (gathered or

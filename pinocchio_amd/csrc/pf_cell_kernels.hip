@@ -62,13 +62,7 @@ __device__ __forceinline__ void pf_group_sum2(double &a, double &b, double *sh /
 // INV: h[0..2] hold the invariants mu1, mu2, mu3 of the tensor (written by k_c2r_invariants) instead of its components
 // SNG: ell() of an ELL_SNG build without TABULATED_CT (src/collapse_times.c:416-426): the ellipsoid of every cell is
 // integrated on its own (pf_sng_core.h)
-// K7 (src/LPT.c:64-93): the 2LPT source and the two 3LPT sources that need only the first-order Hessian, from one
-// cell's six components {11,22,33,12,13,23}; one definition for k_lpt_sources and for the solve that forms them in passing
-PF_HD void pf_lpt_sources_cell(const double d[6], double &src2, double &src31, double &src32) {
-  src2 = d[0] * d[1] + d[0] * d[2] + d[1] * d[2] - d[3] * d[3] - d[4] * d[4] - d[5] * d[5];
-  src31 = 3.0 * (d[0] * (d[1] * d[2] - d[5] * d[5]) - d[3] * (d[3] * d[2] - d[4] * d[5]) + d[4] * (d[3] * d[5] - d[4] * d[1]));
-  src32 = 2.0 * (d[0] + d[1] + d[2]) * src2;
-}
+// K7 (src/LPT.c:64-93), the LPT sources of one cell: pf_lpt_sources_cell, pf_collapse_core.h
 // SRC: the pass of the last radius of a sweep that is followed by compute_LPT_displacements -- the cell's six components are
 // in registers anyway, so its three LPT sources are written here and k_lpt_sources (six more field reads) is not run
 // PR: PRODFLOAT, the type of products.Fmax (float; double in a -DDOUBLE_PRECISION_PRODUCTS build, src/pinocchio.h:219-225)
@@ -208,7 +202,7 @@ __device__ __forceinline__ void pf_collapse_body(const PfCollapseParams &p) {
       pf_lpt_sources_cell(d, src2, src31, src32);
       s2[a] = (F)src2;
       s3a[a] = (F)src31;
-      s3b[a] = (F)src32;
+      if (s3b) s3b[a] = (F)src32;  // (null: the z-pass that contracts into the 3LPT(b) source forms this start value itself, k_c2r_invariants MODE 2)
       sum_src += (double)(F)src2;
     }
     const double delta = INV ? d[0] : d[0] + d[1] + d[2];

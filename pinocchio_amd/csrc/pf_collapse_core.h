@@ -487,6 +487,17 @@ template <bool FAST = false> PF_HD double pf_ell_classic(double l1, double l2, d
 
 // Eigenvalues of the symmetric tensor d = {11,22,33,12,13,23} by the trigonometric formula, ordered by ord()
 // (src/collapse_times.c:679-745).  Returns false for the -10 sentinel branch (q^3 < r^2 or q < 0).
+// K7 (src/LPT.c:64-93): the 2LPT source and the two 3LPT sources that need only the first-order Hessian, from one
+// cell's six components {11,22,33,12,13,23}; one definition for k_lpt_sources, for the solve that forms them in passing and
+// for the z-pass that forms the 3LPT(b) start value where it consumes it (k_c2r_invariants, MODE 2); never contracted.
+PF_HD void pf_lpt_sources_cell(const double d[6], double &src2, double &src31, double &src32) {
+#if defined(__clang__)
+#pragma clang fp contract(off)  // also when included from a translation unit built with contraction on (the z-pass)
+#endif
+  src2 = d[0] * d[1] + d[0] * d[2] + d[1] * d[2] - d[3] * d[3] - d[4] * d[4] - d[5] * d[5];
+  src31 = 3.0 * (d[0] * (d[1] * d[2] - d[5] * d[5]) - d[3] * (d[3] * d[2] - d[4] * d[5]) + d[4] * (d[3] * d[5] - d[4] * d[1]));
+  src32 = 2.0 * (d[0] + d[1] + d[2]) * src2;
+}
 // 3LPT(b) source accumulation of one cell (src/LPT.c:134-137): s -= 2 phi2_ab h_ab over the six components in the
 // reference's order 11,12,13,22,23,33 (storage index 0,3,4,1,5,2), off-diagonal ones twice.  One definition for
 // k_lpt_accum and for the z-pass that forms it on the fly (k_c2r_invariants, MODE 1); never contracted.

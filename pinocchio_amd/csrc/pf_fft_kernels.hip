@@ -82,8 +82,17 @@ template <> struct PfCols<pf_f32x2> {
 };
 
 // FA: addresses as a uniform 64-bit part plus a 32-bit part per lane (pf_addr_uniform; the launcher checks the conditions)
-template <typename F, int N, int T, int DIR, bool FA>
+// DIRS = PF_DIR_XF (an inverse x-pass on one rank): the input is an LPT source spectrum whose forward transform along this axis is
+// still to be done (forward_many stops after its y-pass).  The workgroup does it on the tile it has just loaded -- the stages,
+// twiddles and plan of the stand-alone forward pass k_strided<F, N, T, -1, FA> -- and hands the line back to itself through LDS in
+// the distribution a load would have given (pf_line_index): from there on `src` holds bit for bit what the forward kernel would
+// have stored and this one loaded, and the spectrum's round trip through HBM (one field written, one read) is gone.
+// (A value of the direction argument, not one more template argument: the plain instantiations keep their names and their code.)
+constexpr int PF_DIR_XF = 2;
+template <typename F, int N, int T, int DIRS, bool FA>
 __global__ void __launch_bounds__(T *N / 8) __attribute__((amdgpu_waves_per_eu(4))) k_strided(const PfStridedParams p, const long long nwork, const int ntiles) {
+  constexpr bool XF = DIRS == PF_DIR_XF;
+  constexpr int DIR = XF ? +1 : DIRS;
   using C = pfc<F>;
   using COLS = PfCols<F>;
   using S = typename COLS::S;  // scalar of the field in memory
@@ -130,6 +139,19 @@ __global__ void __launch_bounds__(T *N / 8) __attribute__((amdgpu_waves_per_eu(4
     }
   };
   load_tile(p.job[0].in, tl, col);
+  if constexpr (XF) {
+    // (columns beyond the last valid one hold zeros and stay zeros; the launcher gives every job the same input and no band)
+    PfStages<F, N, -1, 1, 0, false, P16>::run(
+        src, tl, tw, [&](int pos, C val) { lds[pos * T + c] = val; }, [&](int pos) { return lds[pos * T + c]; });
+    if constexpr (P16) {  // line order (register m = point tl + m NT) -> the paired plan's input order; the plain plan loads in line order
+#pragma unroll
+      for (int m = 0; m < 8; m++) lds[(tl + m * NT) * T + c] = src[m];
+      __syncthreads();
+#pragma unroll
+      for (int m = 0; m < 8; m++) src[m] = lds[pf_line_index<N, P16>(tl, m) * T + c];
+      __syncthreads();
+    }
+  }
   // first pass: window of the two untransformed axes times the growth factor, one exp per thread and column (none without
   // smoothing).  Formed here, outside the loop over jobs: inside it the constants of exp() would live in ~24 registers
   // through every job of the kernel.
@@ -384,6 +406,9 @@ __global__ void __launch_bounds__(TL *(N / 16)) k_c2r_persistent(const PfC2RPara
 // MODE 1 (the Hessian of the 2LPT potential, src/LPT.c:112-137): the six rows are not stored at all; each cell's 3LPT(b)
 // source is updated in place from them and the six components of the first-order Hessian (read from job[c].out):
 // p.acc -= 2 phi2_ab h_ab, by the same pf_lpt3b_accumulate as k_lpt_accum.
+// MODE 2: MODE 1 on a source field that does not hold its start value yet -- 2 (h11 + h22 + h33) S2(h), a function of the six
+// first-order components the reduction has loaded anyway, formed by the solve's own pf_lpt_sources_cell and rounded to the
+// field type as the solve would have stored it: p.acc is only written (one field less written by the solve, one less read here).
 // Round 4: fp64 rows of 512 points and more run THREE workgroups per CU instead of two.  The row of an iteration is loaded at the
 // top of that iteration (PF_ZI_PREFETCH = 0: no row carried in registers across the stages: 78 instead of 114 registers) and the
 // exchange area of a line is padded by p >> 4 instead of p >> 3 (544 instead of 576 complex per 512-point line: 52.2 KB per
@@ -539,7 +564,13 @@ PF_ZI_PRAGMA(unroll PF_ZI_RUNROLL)
           ha[k] = (double)g.x; hb[k] = (double)g.y;
         }
         F2 *acc = reinterpret_cast<F2 *>(reinterpret_cast<F *>(p.acc) + a);
-        const F2 s = *acc;
+        F2 s;
+        if constexpr (MODE == 2) {
+          double s2, s31, sa, sb;
+          pf_lpt_sources_cell(ha, s2, s31, sa);
+          pf_lpt_sources_cell(hb, s2, s31, sb);
+          s.x = (F)sa; s.y = (F)sb;
+        } else s = *acc;
         F2 r;
         r.x = (F)pf_lpt3b_accumulate((double)s.x, da, ha);
         r.y = (F)pf_lpt3b_accumulate((double)s.y, db, hb);
@@ -988,6 +1019,12 @@ static int launch_strided_f32(const PfStridedParams &p, hipStream_t st) {
   else return launch_strided_n<float, N, DIR>(p, st);
 }
 
+template <int N>
+static int launch_strided_xf_f32(const PfStridedParams &p, hipStream_t st) {
+  if constexpr (N < 1024) return launch_strided_n<float, N, PF_DIR_XF>(p, st);
+  else return 2;
+}
+
 template <typename F, int N>
 static int launch_c2r_n(const PfC2RParams &p, hipStream_t st) {
   constexpr int M = N / 2, NT = M / 8;
@@ -1025,6 +1062,9 @@ static int launch_c2r_invariants_n(const PfC2RParams &p, hipStream_t st, int mod
   if (mode == 1) {
     if constexpr (PfZiPlan<F, M>::spec(1)) hipLaunchKernelGGL((k_c2r_invariants_spec<F, N, 1>), dim3((unsigned)g), dim3(6 * NT + 64 * PfZiPlan<F, M>::reducer_waves), shm, st, p, p.nlines);
     else hipLaunchKernelGGL((k_c2r_invariants<F, N, 1>), dim3((unsigned)g), dim3(6 * NT), shm, st, p, p.nlines);
+  } else if (mode == 2) {
+    if constexpr (PfZiPlan<F, M>::spec(1)) hipLaunchKernelGGL((k_c2r_invariants_spec<F, N, 2>), dim3((unsigned)g), dim3(6 * NT + 64 * PfZiPlan<F, M>::reducer_waves), shm, st, p, p.nlines);
+    else hipLaunchKernelGGL((k_c2r_invariants<F, N, 2>), dim3((unsigned)g), dim3(6 * NT), shm, st, p, p.nlines);
   } else if constexpr (PF_ZI_PK2 && sizeof(F) == 4 && N >= 512 && N <= PF_ZI_PK2_MAXN) {
     // fp32 rows of 512 and 1024 points: two rows per thread (k_c2r_invariants_pk2); a job with the factor i k has no place in the sweep's z-pass
     for (int j = 0; j < 6; j++) if (p.job[j].mul == PF_MUL_IK) return 2;
@@ -1096,6 +1136,24 @@ int pf_launch_strided(int fb, int n, int dir, const PfStridedParams &p, hipStrea
   }
 }
 
+// The inverse x-pass with the forward x-transform of its input in front (k_strided, PF_DIR_XF): the lengths and field types whose plain
+// passes are k_strided itself -- fp64 fields, and fp32 lines below 1024 points (longer ones run the packed kernels of pf_fft16_kernels.hip)
+bool pf_strided_xfuse_supported(int fb, int n) { return !(n & (n - 1)) && n >= 16 && n <= 2048 && (fb == 8 || n < 1024); }
+int pf_launch_strided_xfuse(int fb, int n, const PfStridedParams &p, hipStream_t st) {
+  if (!pf_strided_xfuse_supported(fb, n) || p.njobs < 1 || p.band_e < n / 2 || p.band_outer < n / 2 || p.out_ne > 0) return 2;
+  for (int j = 1; j < p.njobs; j++) if (p.job[j].in != p.job[0].in) return 2;  // the tile is transformed once, for every job
+  for (int j = 0; j < p.njobs; j++) if (p.job[j].out == p.job[0].in) return 2; // the input keeps its pending form
+  if (fb == 8) {
+#define CALL(NN) launch_strided_n<double, NN, PF_DIR_XF>(p, st)
+    PF_SWITCH_N(n, CALL)
+#undef CALL
+  } else {
+#define CALL(NN) launch_strided_xf_f32<NN>(p, st)
+    PF_SWITCH_N(n, CALL)
+#undef CALL
+  }
+}
+
 int pf_launch_c2r(int fb, int n, const PfC2RParams &p, hipStream_t st) {
   if (n & (n - 1)) return pf_launch_mixed_c2r(fb, n, p, st);
   if (fb == 8) {
@@ -1123,9 +1181,9 @@ bool pf_c2r_invariants_preferred(int fb, int n) {
   return pf_c2r_invariants_supported(fb, n) && (!(n & (n - 1)) || (fb == 8 && pf_mixed_plan_compiled_in(n)));
 }
 int pf_launch_c2r_invariants(int fb, int n, const PfC2RParams &p, hipStream_t st, int mode) {
-  if (p.njobs != 6 || (mode == 1 && !p.acc) || (mode == 0 && !p.flag) || !pf_c2r_invariants_supported(fb, n)) return 2;
+  if (p.njobs != 6 || (mode >= 1 && !p.acc) || (mode == 0 && !p.flag) || mode < 0 || mode > 2 || !pf_c2r_invariants_supported(fb, n)) return 2;
   if (fb == 4 && mode == 0 && (!p.inv_out[0] || !p.inv_out[1] || !p.inv_out[2])) return 2;
-  if (n & (n - 1)) return pf_launch_mixed_c2r_invariants(fb, n, p, st, mode);
+  if (n & (n - 1)) return mode == 2 ? 2 : pf_launch_mixed_c2r_invariants(fb, n, p, st, mode);  // (the mixed-radix z-pass reads its start value)
   if (fb == 8) {
 #define CALL(NN) launch_c2r_invariants_n<double, NN>(p, st, mode)
     PF_SWITCH_N(n, CALL)

@@ -27,6 +27,8 @@ struct PfTuning {
   bool preflight;           // PF_PREFLIGHT: pf_create holds the plan's bytes against the device's free memory before it allocates
   bool distribute_lds;      // PF_DISTRIBUTE_LDS: pf_distribute stages the records of a round in LDS (1, default) or writes one lane per record (0)
   bool gtab;                // PF_GTAB: the inverse growing mode of the fast flavour from the polynomial table (pf_gtab.h)
+  bool lpt3b_start;         // PF_LPT3B_START: 1 = the solve of the sweep's last radius stores the 3LPT(b) start value and the contracting z-pass reads it (0: that z-pass forms it)
+  bool lpt_xfuse;           // PF_LPT_XFUSE: one rank, the forward x-pass of an LPT source runs inside the inverse x-passes that read it (k_strided with PF_DIR_XF)
 };
 
 // multiplier applied along the transformed axis before the 1-D transform
@@ -74,6 +76,9 @@ struct PfStridedParams {
 
 // one x- or y-pass: for every job, out = FFT_e[ in * pre * mul ]  (dir = +1 inverse, -1 forward)
 int pf_launch_strided(int field_bytes, int n, int dir, const PfStridedParams &p, hipStream_t st);
+// dir = +1 with the forward transform of the (single) input along the same axis done first, in the same workgroup (k_strided with PF_DIR_XF)
+bool pf_strided_xfuse_supported(int field_bytes, int n);
+int pf_launch_strided_xfuse(int field_bytes, int n, const PfStridedParams &p, hipStream_t st);
 int pf_launch_exp_table(double *etab, int n, double rs, hipStream_t st);
 // 2048-point fp32 lines, sixteen points per thread (pf_fft16_kernels.hip); -1: not a case of that kernel
 int pf_launch_strided16(int field_bytes, int n, int dir, const PfStridedParams &p, hipStream_t st);
