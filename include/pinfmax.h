@@ -478,9 +478,57 @@ int pf_distribute_sorted_neighbours_map(pf_ctx *ctx, double flast, pf_map *m, in
    starts, lookups) of the calling thread's last context-free pf_neighbours that ran under PF_NEIGH_STATS=1 (read per call: such a
    call brackets the two parts with HIP events; the default records nothing and the call refuses) */
 int pf_debug_neigh_ms(double *sort_ms, double *table_ms);
+/* distribute_back() (src/distribute.c:703-946): the one data-parallel step BEHIND the group construction.  build_groups() leaves
+   frag[].zacc and frag[].group_ID for the stored particles of every sub-box; the reference scatters those of the good particles
+   into products[] of the FFT slabs, where write_timeless_snapshot() (src/write_snapshot.c:859-905) reads them for its ZACC and
+   GRUP blocks.  Here they go into two per-cell columns of this rank's slab in HBM -- zacc of the product precision (float, or
+   double with PF_FLAG_DOUBLE_PRODUCTS), group_ID int; index z + n*(y + n*x_local) as every product column; zacc = -1 and
+   group_ID = 0 before anything is written (src/allocations.c:519-524).  The columns do not exist until one of these calls, or a
+   ZACC / GRUP request to pf_get_block, needs them: 8 bytes per cell (12 with double products), counted into pf_device_bytes from
+   then on and freed by pf_destroy; when they cannot be allocated the call says how many bytes it needs and the context stays as it
+   was.  They depend on no sweep -- none of these calls needs computed products -- and no sweep touches them.  Every call is
+   ordered on the context's stream: a block read after a back call sees it.
+   pf_back_reset: zacc := -1, group_ID := 0.
+   pf_distribute_back: keep_data_back() (:799-837), which is also the loop of send_data_back() (:859-896), with THIS rank's slab as
+   the receiving fft box.  box = subbox.stabl, subbox.Lgwbl, subbox.safe of the sub-box the arrays belong to, checked as
+   pf_map_create checks its box; a direction is periodic when len[d] == n.  frag_pos[iz] is the sub-box-space index
+   z + Lz (y + Ly x) of particle iz; frag_pos == NULL is the CLASSIC_FRAGMENTATION form, particle iz at position iz (:808-809).
+   zacc points at the first particle's value and zacc_stride is the byte distance to the next -- a packed array, or
+   (char *)frag + off_zacc and sizeof(product_data) --, float, or double for a double-products context; group_id / group_stride
+   likewise.  Particle iz is taken when it is a good particle, safe[d] <= c[d] < len[d] - safe[d] in all three directions with
+   c = INDEX_TO_COORD(frag_pos[iz]) (:815-817), and its global cell (c[d] + start[d]) mod n -- the start first reduced to the
+   periodic box, as pf_distribute does -- lies in this rank's x-slab (:824-827); both columns are then written at
+   z + n*(y + n*(x - x0)) (:830-832).  *stored (may be NULL) is the number written on this rank, 64-bit and independent of the
+   schedule.  Not collective and without an exchange: the owner of the sub-box, or whoever carries its arrays, calls it on every
+   rank whose slab the sub-box meets; a box that misses the slab stores nothing; count = 0 is valid.  Positions are unique within
+   a sub-box and the good regions of different sub-boxes are disjoint; of duplicates passed anyway one is kept, which is
+   unspecified.
+   pf_back_apply: recv_data_back() (:911-946) -- entries whose position in THIS rank's fft box the sender has computed already
+   (back_data of the reference's unmodified send_data_back: pos, zacc, group_ID, each with its stride).
+   Refused, with nothing written to the columns and no scatter launched (everything is validated on the host while it is staged,
+   before the first launch): a frag_pos entry that is not below Lx Ly Lz (or, with frag_pos NULL, count above it); a pos entry of
+   pf_back_apply that is not below the cells of the slab; more than 2^32 entries; a stride that is no multiple of the element
+   size; a bad box; null arrays with count > 0.  The three arrays go up through the hand-off pieces (PF_HANDOFF_CHUNK_MB),
+   packed by the host threads -- 12 bytes per particle (16 with double products) and nothing else of the records -- and one
+   kernel scatters them.
+   pf_update_back: the two columns merged into host records the caller holds (products[i].zacc / .group_ID of a -DSNAPSHOT
+   build), as pf_update_products merges the others: stride and offsets are multiples of four, a negative offset skips that
+   field, every other byte of a record keeps its value; only the 8 (12) bytes per cell cross the link.
+   pf_debug_distribute_back: test tap without a context -- the same kernel on the slab planes x0 .. x0 + nxl - 1 of an n^3 box,
+   float zacc, columns that start at -1 / 0 and are returned whole. */
+int pf_back_reset(pf_ctx *ctx);
+int pf_distribute_back(pf_ctx *ctx, const pf_peak_region *box, size_t count, const unsigned int *frag_pos, const void *zacc,
+                       size_t zacc_stride, const int *group_id, size_t group_stride, size_t *stored);
+int pf_back_apply(pf_ctx *ctx, size_t count, const unsigned int *pos, size_t pos_stride, const void *zacc, size_t zacc_stride,
+                  const int *group_id, size_t group_stride);
+int pf_update_back(pf_ctx *ctx, void *products_host, size_t stride, long off_zacc, long off_group_ID);
+int pf_debug_distribute_back(int n, int x0, int nxl, const pf_peak_region *box, size_t count, const unsigned int *frag_pos,
+                             const float *zacc, const int *group_id, float *zacc_out, int *group_out, size_t *stored);
 /* Per-particle payload of one block of the "timeless snapshot" (write_timeless_snapshot, src/write_snapshot.c:207-342)
    for this rank's slab, from the SoA columns in HBM: name = "ID  " (1 + global index as MYIDTYPE of id_bytes = 4 or 8,
-   :648-664), "FMAX" float, "RMAX" int, "ZEL " / "2LPT" / "31PT" / "32PT" float[3] per particle (:700-855). */
+   :648-664), "FMAX" float, "RMAX" int, "ZEL " / "2LPT" / "31PT" / "32PT" float[3] per particle (:700-855), and the last
+   two blocks of the file, "ZACC" float and "GRUP" int per particle (:859-905), from the columns of the back calls above --
+   these two need no computed products and read -1 / 0 where nothing was distributed back. */
 int pf_get_block(pf_ctx *ctx, const char *name, int id_bytes, void *host);
 /* debug / test taps (host copies, fp64): second_derivatives[0][i] of the last
    pf_second_derivatives (i = 0..5 <-> 11,22,33,12,13,23; src/LPT.c:36-44),

@@ -133,6 +133,12 @@ PROTOTYPES = {
     "pf_distribute_sorted_neighbours_map": (C.c_int, [_vp, C.c_double, _vp, C.c_int, C.POINTER(ProductLayout), C.c_size_t, _vp, C.POINTER(C.c_uint),
                                                       C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ubyte),
                                                       C.POINTER(C.c_ulonglong), C.POINTER(C.c_size_t)]),
+    "pf_back_reset": (C.c_int, [_vp]),
+    "pf_distribute_back": (C.c_int, [_vp, C.POINTER(PeakRegion), C.c_size_t, C.POINTER(C.c_uint), _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "pf_back_apply": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t]),
+    "pf_update_back": (C.c_int, [_vp, _vp, C.c_size_t, C.c_long, C.c_long]),
+    "pf_debug_distribute_back": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(PeakRegion), C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "pf_set_collapse_model": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "pf_set_modified_gravity": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "pf_set_tabulated_ct": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),

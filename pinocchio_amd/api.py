@@ -156,6 +156,49 @@ def neighbours(frag_pos, fmax, start, length, safe):
     return _neighbours(_lib.load(), None, frag_pos, fmax, start, length, safe, np.float32)
 
 
+def _strided(a, dtype, count, what):
+    """a packed array or a field of a structured record array -> (array kept alive, pointer to its first element, byte stride)"""
+    a = np.asarray(a)
+    if a.dtype != dtype:
+        a = a.astype(dtype)
+    if a.ndim != 1 or a.size != count:
+        raise ValueError(f"{what} of shape {a.shape} for {count} entries")
+    if count > 1 and a.strides[0] <= 0:
+        a = np.ascontiguousarray(a)
+    return a, C.c_void_p(a.ctypes.data), (a.strides[0] if count > 1 else a.dtype.itemsize)
+
+
+def _frag_pos(frag_pos, zacc):
+    """frag_pos None: the CLASSIC_FRAGMENTATION form, particle iz at position iz"""
+    if frag_pos is None:
+        return None, None, int(np.asarray(zacc).size)
+    pos = np.ascontiguousarray(frag_pos, dtype=np.uint32).ravel()
+    return pos, pos.ctypes.data_as(C.POINTER(C.c_uint)), pos.size
+
+
+def distribute_back(n: int, x0: int, nxl: int, start, length, safe, frag_pos, zacc, group_id):
+    """keep_data_back (src/distribute.c:799-837) by the device kernel without a context (pf_debug_distribute_back): zacc (fp32) and
+    group_id of the particles at the sub-box positions frag_pos (None: particle iz at position iz) of the sub-box (start, length,
+    safe) scattered into the slab planes x0 .. x0 + nxl - 1 of an n^3 box whose columns start at -1 / 0
+    -> (zacc[nxl n n], group_ID[nxl n n], stored)"""
+    L = _lib.load()
+    pos, pp, count = _frag_pos(frag_pos, zacc)
+    z = np.ascontiguousarray(zacc, dtype=np.float32).ravel()
+    g = np.ascontiguousarray(group_id, dtype=np.int32).ravel()
+    if z.size != count or g.size != count:
+        raise ValueError(f"{z.size} zacc and {g.size} group_ID for {count} particles")
+    nc = max(int(nxl), 0) * int(n) * int(n)
+    zout = np.empty(nc, dtype=np.float32)
+    gout = np.empty(nc, dtype=np.int32)
+    rg = _region((start, length, safe))
+    stored = C.c_size_t()
+    if L.pf_debug_distribute_back(int(n), int(x0), int(nxl), C.byref(rg), count, pp, z.ctypes.data_as(C.POINTER(C.c_float)),
+                                  g.ctypes.data_as(C.POINTER(C.c_int)), zout.ctypes.data_as(C.POINTER(C.c_float)),
+                                  gout.ctypes.data_as(C.POINTER(C.c_int)), C.byref(stored)):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_distribute_back failed")
+    return zout, gout, int(stored.value)
+
+
 _WHICH = {"current": _lib.MAP_CURRENT, "update": _lib.MAP_UPDATE}
 
 
@@ -611,6 +654,47 @@ class Fmax:
         transfers through the hand-off pieces (pf_neighbours)"""
         return _neighbours(self.L, self.h, frag_pos, fmax, start, length, safe, np.float64 if self.double_products else np.float32)
 
+    # -- distribute_back (src/distribute.c:703-946): zacc and group_ID back to the slab -----------------------------------
+    @property
+    def _zacc_dtype(self):
+        return np.float64 if self.double_products else np.float32
+
+    def back_reset(self):
+        """zacc := -1, group_ID := 0 in the two columns of this slab (src/allocations.c:519-524); allocates them at first use"""
+        self._chk(self.L.pf_back_reset(self.h))
+
+    def distribute_back(self, start, length, safe, frag_pos, zacc, group_id) -> int:
+        """keep_data_back / the loop of send_data_back (src/distribute.c:799-896) with this rank's slab as the receiving fft box
+        (pf_distribute_back): of the particles at the sub-box positions frag_pos (None: particle iz at position iz) of the sub-box
+        (start, length, safe) = (subbox.stabl, subbox.Lgwbl, subbox.safe) the good ones whose global cell lies in this slab have
+        their zacc (the context's product precision) and group_id stored in the columns -> how many were.  zacc and group_id are
+        packed arrays or fields of a structured record array (frag["zacc"]): only the values are uploaded.  Not collective."""
+        pos, pp, count = _frag_pos(frag_pos, zacc)
+        z, zp, zs = _strided(zacc, self._zacc_dtype, count, "zacc")
+        g, gp, gs = _strided(group_id, np.int32, count, "group_ID")
+        rg = _region((start, length, safe))
+        stored = C.c_size_t()
+        self._chk(self.L.pf_distribute_back(self.h, C.byref(rg), count, pp, zp, zs, gp, gs, C.byref(stored)))
+        return int(stored.value)
+
+    def back_apply(self, pos, zacc, group_id):
+        """recv_data_back (src/distribute.c:911-946): entries whose position in THIS slab the sender computed (the back_data of the
+        reference's send_data_back); each argument a packed array or a field of a record array (pf_back_apply)"""
+        count = int(np.asarray(pos).size)
+        p, ppos, ps = _strided(pos, np.uint32, count, "pos")
+        z, zp, zs = _strided(zacc, self._zacc_dtype, count, "zacc")
+        g, gp, gs = _strided(group_id, np.int32, count, "group_ID")
+        self._chk(self.L.pf_back_apply(self.h, count, ppos, ps, zp, zs, gp, gs))
+
+    def update_back(self, records: np.ndarray, off_zacc: int, off_group_ID: int) -> np.ndarray:
+        """merge the zacc / group_ID columns into caller-held records of this slab's cells (products[i].zacc / .group_ID) at the
+        given byte offsets; a negative offset skips that field, every other byte keeps its value (pf_update_back)"""
+        nc = self.nxl * self.n * self.n
+        if not (records.flags.c_contiguous and records.flags.writeable and records.nbytes % nc == 0):
+            raise ValueError(f"records of {records.nbytes} bytes for {nc} cells")
+        self._chk(self.L.pf_update_back(self.h, records.ctypes.data_as(C.c_void_p), records.nbytes // nc, int(off_zacc), int(off_group_ID)))
+        return records
+
     def organize(self, records: np.ndarray, frag_pos: np.ndarray, layout=None):
         """sort_and_organize() (src/fragment.c:484-520) on records the caller holds (contributions of several ranks to one
         sub-box, concatenated): `records` (a structured array of product_layout(), or rows of layout.stride bytes) and `frag_pos`
@@ -633,9 +717,9 @@ class Fmax:
         nc = self.nxl * self.n * self.n
         if name == "ID  ":
             out = np.empty(nc, dtype=np.uint64 if id_bytes == 8 else np.uint32)
-        elif name == "RMAX":
+        elif name in ("RMAX", "GRUP"):
             out = np.empty(nc, dtype=np.int32)
-        elif name == "FMAX":
+        elif name in ("FMAX", "ZACC"):
             out = np.empty(nc, dtype=np.float32)
         else:
             out = np.empty((nc, 3), dtype=np.float32)

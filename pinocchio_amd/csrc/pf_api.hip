@@ -156,6 +156,10 @@ struct pf_ctx {
   void *fmax, *vel12;
   int pb;
   int *rmax;
+  // distribute_back() (pf_back.hip): zacc (PRODFLOAT) and group_ID of every cell of the slab.  Null until a back call or a ZACC / GRUP
+  // block request needs them (pf_ctx_back_columns); no sweep touches them
+  void *back_zacc;
+  int *back_group;
   double *partials;    // 2 * PF_NBLK
   double *scal;        // device scalars, see SC_*
   unsigned long long *hist;
@@ -527,7 +531,7 @@ extern "C" int pf_create(pf_ctx **out, const pf_config *cfg) {
   for (int i = 0; i < 6; i++) { c->B[i] = nullptr; c->B2[i] = nullptr; }
   c->blockA = nullptr; c->dk = nullptr; c->recvA = nullptr; c->tw = nullptr;
   c->blockA2 = nullptr; c->recvA2 = nullptr; c->cstream = nullptr; c->dk_full = nullptr; c->replicate = false; c->dk_full_valid = false; for (int k = 0; k < 3; k++) c->INV[0][k] = c->INV[1][k] = nullptr; c->inv_w = 0; c->inv_own[0] = c->inv_own[1] = nullptr; c->blockS = c->blockB2 = nullptr;
-  c->fmax = nullptr; c->rmax = nullptr; c->vel12 = nullptr; c->partials = nullptr; c->scal = nullptr; c->hist = nullptr; c->spl = nullptr;
+  c->fmax = nullptr; c->rmax = nullptr; c->vel12 = nullptr; c->back_zacc = nullptr; c->back_group = nullptr; c->partials = nullptr; c->scal = nullptr; c->hist = nullptr; c->spl = nullptr;
   c->gtab = nullptr; c->etab = nullptr; c->ct_block = nullptr; c->gt = nullptr; c->gt_lut = nullptr;
   memset(c->gt_ok, 0, sizeof(c->gt_ok)); memset(c->gt_err, 0, sizeof(c->gt_err));
   for (int i = 0; i < 2; i++) c->ev_x[i] = c->ev_r[i] = c->ev_y[i] = c->ev_s[i] = nullptr;
@@ -558,7 +562,7 @@ extern "C" int pf_destroy(pf_ctx *c) {
   hipFree(c->dk); hipFree(c->blockA); hipFree(c->recvA); hipFree(c->tw); hipFree(c->blockA2); hipFree(c->recvA2); hipFree(c->dk_full); hipFree(c->inv_own[0]); hipFree(c->inv_own[1]);
   for (int i = 0; i < 6; i++) hipFree(c->B[i]);
   hipFree(c->blockS); hipFree(c->blockB2);
-  hipFree(c->fmax); hipFree(c->rmax); hipFree(c->vel12); hipFree(c->partials); hipFree(c->partials_src); hipFree(c->scal); hipFree(c->hist); hipFree(c->spl); hipFree(c->gt); hipFree(c->gt_lut); hipFree(c->gtab); hipFree(c->etab); hipFree(c->ct_block); hipFree(c->W);
+  hipFree(c->fmax); hipFree(c->rmax); hipFree(c->vel12); hipFree(c->back_zacc); hipFree(c->back_group); hipFree(c->partials); hipFree(c->partials_src); hipFree(c->scal); hipFree(c->hist); hipFree(c->spl); hipFree(c->gt); hipFree(c->gt_lut); hipFree(c->gtab); hipFree(c->etab); hipFree(c->ct_block); hipFree(c->W);
   pf_gfft_destroy(c->fft_c2r);
   if (c->fft_r2c != c->fft_c2r) pf_gfft_destroy(c->fft_r2c);
   for (auto &e : c->evs) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
@@ -1962,6 +1966,77 @@ extern "C" int pf_update_products(pf_ctx *c, void *host, const pf_product_layout
   return 0;
 }
 
+// ---- the zacc / group_ID columns of distribute_back() (pf_back.hip) ----
+int pf_ctx_back_columns(pf_ctx *c, const char *who, void **zacc, int **group, bool *fresh) {
+  *fresh = false;
+  if (!c->back_zacc) {
+    const size_t nc = ncell(c), bytes = nc * ((size_t)c->pb + sizeof(int));
+    void *z = nullptr; int *g = nullptr;
+    if (hipMalloc(&z, nc * (size_t)c->pb) != hipSuccess || hipMalloc((void **)&g, nc * sizeof(int)) != hipSuccess) {
+      (void)hipGetLastError();
+      hipFree(z); hipFree(g);
+      return pf_fail(c->rank, "%s: cannot allocate the %zu bytes of the zacc and group_ID columns on the device (%.1f GB held by this context)", who, bytes,
+                     1e-9 * c->dev_bytes);
+    }
+    if (pf_launch_back_fill(c->pb, z, g, nc, c->stream)) {
+      hipFree(z); hipFree(g);
+      return pf_fail(c->rank, "%s: launch failed", who);
+    }
+    c->back_zacc = z; c->back_group = g; c->dev_bytes += bytes;
+    *fresh = true;
+  }
+  *zacc = c->back_zacc; *group = c->back_group;
+  return 0;
+}
+
+// The two columns into records the caller holds -- products[i].zacc / .group_ID of a -DSNAPSHOT build --, the merge of
+// pf_update_products: the columns travel as they lie (8 bytes per cell, 12 with double products), a piece of each in one pinned
+// buffer, and the host threads scatter them into the records while the next piece travels.
+extern "C" int pf_update_back(pf_ctx *c, void *host, size_t stride, long off_zacc, long off_group_ID) {
+  const char *who = "pf_update_back";
+  if (!c || !host) return pf_fail(0, "%s: null argument", who);
+  if (stride < 4 || stride % 4) return pf_fail(c->rank, "%s: bad stride %zu", who, stride);
+  const size_t pb = (size_t)c->pb;
+  if ((off_zacc >= 0 && off_zacc % 4) || (off_group_ID >= 0 && off_group_ID % 4)) return pf_fail(c->rank, "%s: the offsets %ld and %ld must be multiples of four", who, off_zacc, off_group_ID);
+  const bool wz = off_zacc >= 0, wg = off_group_ID >= 0;
+  if ((wz && (size_t)off_zacc + pb > stride) || (wg && (size_t)off_group_ID + 4 > stride) ||
+      (wz && wg && off_zacc < off_group_ID + 4 && off_group_ID < off_zacc + (long)pb))
+    return pf_fail(c->rank, "%s: the two fields overlap or leave the record", who);
+  if (!wz && !wg) return 0;
+  void *zcol; int *gcol; bool fresh;
+  if (pf_ctx_back_columns(c, who, &zcol, &gcol, &fresh)) return 1;
+  PhaseTimer pt(c, 3);
+  const size_t nc = ncell(c);
+  PfHandoff *h;
+  if (handoff_get(c, &h)) return 1;
+  PFCHK(c, handoff_begin(c, h));
+  const size_t per = (h->chunk / (pb + 4)) & ~(size_t)1;   // cells of a piece: zacc at the front of the buffer, group_ID behind (8-byte aligned)
+  if (!per) return pf_fail(c->rank, "%s: a cell does not fit the staging pieces", who);
+  const size_t np = (nc + per - 1) / per;
+  auto issue = [&](size_t k) -> int {
+    const int b = (int)(k & 1);
+    const size_t first = k * per, cnt = nc - first < per ? nc - first : per;
+    if (wz) HIPCHK(c, hipMemcpyAsync(h->pin[b], (const char *)zcol + first * pb, cnt * pb, hipMemcpyDeviceToHost, h->st[b]));
+    if (wg) HIPCHK(c, hipMemcpyAsync(h->pin[b] + per * pb, gcol + first, cnt * sizeof(int), hipMemcpyDeviceToHost, h->st[b]));
+    return 0;
+  };
+  if (issue(0)) return 1;
+  for (size_t k = 0; k < np; k++) {
+    if (k + 1 < np && issue(k + 1)) return 1;
+    const int b = (int)(k & 1);
+    HIPCHK(c, hipStreamSynchronize(h->st[b]));
+    const size_t first = k * per, cnt = nc - first < per ? nc - first : per;
+    char *dst = (char *)host + first * stride; const char *sz = h->pin[b], *sg = h->pin[b] + per * pb;
+    h->pool->run(cnt, [=](size_t a, size_t e) {
+      for (size_t i = a; i < e; i++) {
+        if (wz) memcpy(dst + i * stride + off_zacc, sz + i * pb, pb);
+        if (wg) memcpy(dst + i * stride + off_group_ID, sg + i * 4, 4);
+      }
+    });
+  }
+  return 0;
+}
+
 // first stage of fragmentation on the device (pf_select_sort.hip)
 extern "C" int pf_select_sorted(pf_ctx *c, float flast, size_t capacity, unsigned int *cell_index, float *fmax, size_t *count) {
   if (!c || !count) return pf_fail(0, "pf_select_sorted: null argument");
@@ -2321,6 +2396,13 @@ void pf_ctx_timer_end(void *t, int phase) { if (phase) delete (PhaseTimer *)t; e
 // per-particle payload of one block of the timeless snapshot (src/write_snapshot.c:207-342, 620-855)
 extern "C" int pf_get_block(pf_ctx *c, const char *name, int id_bytes, void *host) {
   if (!c || !name || !host) return pf_fail(0, "pf_get_block: null argument");
+  if (!strncmp(name, "ZACC", 4) || !strncmp(name, "GRUP", 4)) {  // :859-905, the columns of distribute_back(): they need no sweep
+    if (c->pb != 4) return pf_fail(c->rank, "pf_get_block: the fp32 snapshot blocks are served from fp32 products only (not with PF_FLAG_DOUBLE_PRODUCTS)");
+    void *zcol; int *gcol; bool fresh;
+    if (pf_ctx_back_columns(c, "pf_get_block", &zcol, &gcol, &fresh)) return 1;
+    const bool z = name[0] == 'Z';
+    return handoff_d2h(c, (char *)host, z ? (const char *)zcol : (const char *)gcol, ncell(c) * 4, 4, no_fill);
+  }
   if (!c->products_init) return pf_fail(c->rank, "pf_get_block: products not computed");
   if (c->pb != 4) return pf_fail(c->rank, "pf_get_block: the fp32 snapshot blocks are served from fp32 products only (not with PF_FLAG_DOUBLE_PRODUCTS)");
   PFCHK(c, velocities_ready(c));

@@ -328,6 +328,13 @@ int pf_ctx_h2d_packed(pf_ctx *c, void *dst_dev, const void *host, size_t count, 
 int pf_distribute_sorted_impl(const char *who, pf_ctx *c, double flast, const pf_subbox *sub, const unsigned int *map_host, const unsigned int *map_dev,
                               const pf_product_layout *l, size_t capacity, void *frag, unsigned int *frag_pos, unsigned int *sorted_pos, int *indices,
                               size_t *count, const PfNeighOut *nb = nullptr);
+// ---- pf_back.hip: distribute_back() (src/distribute.c:703-946) into the zacc / group_ID columns of the slab ----
+// zacc := -1 (pb bytes each), group_ID := 0 (src/allocations.c:519-524)
+int pf_launch_back_fill(int pb, void *zacc, int *group, size_t ncell, hipStream_t st);
+// the two columns of the context (pf_api.hip).  They come into being at the first call -- allocated, counted into pf_device_bytes and
+// set to -1 / 0 on the context's stream; *fresh says that this call did it --, and a failure (message of `who` with the bytes it needs)
+// leaves the context without them, as it was
+int pf_ctx_back_columns(pf_ctx *c, const char *who, void **zacc, int **group, bool *fresh);
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);
