@@ -83,7 +83,9 @@ typedef struct {
 /* Device memory a context of this configuration holds, in bytes: *at_create by pf_create itself, *peak once a sweep and the LPT part
    have run (the second field set is allocated at first use).  pf_create compares *peak with the free memory of the device
    (hipMemGetInfo) BEFORE allocating anything and fails in the usual format when it does not fit (PF_PREFLIGHT=0: no check).  The
-   host's counterpart of the memory report of src/allocations.c:60-160.  Needs no device. */
+   host's counterpart of the memory report of src/allocations.c:60-160.  Needs no device.  Not in the plan: the columns that come
+   into being at first use -- zacc / group_ID of the back calls, and the twelve Vel*_prev columns of pf_shift_displacements, 48
+   bytes per cell (96 with double products) until pf_drop_prev. */
 int pf_plan_bytes(const pf_config *cfg, size_t *at_create, size_t *peak);
 
 /* --- life cycle: replaces set_one_grid + compute_fft_plans + the FFT-buffer
@@ -338,7 +340,8 @@ int pf_debug_peaks(int n, const float *fmax_host, double flast, const pf_peak_re
    word, bit p % 32 of word p / 32, prod(len) bits: frag_map_update / frag_map through build_distmap, :670-682; NULL = every bit
    set) and (double)Fmax >= flast (update_distmap, :685-698).  NaN is never taken.
    Output: every taken cell appends one record in the caller's layout to `frag` -- the conventions of pf_get_products; bytes no
-   non-negative offset names are zero (the *_prev fields of a RECOMPUTE_DISPLACEMENTS build among them); stride and offsets are
+   non-negative offset names are zero (the *_prev fields of a RECOMPUTE_DISPLACEMENTS build among them: pf_refresh_velocities
+   fills those); stride and offsets are
    multiples of four -- and its sub-box-space index to `frag_pos`.  *count receives the number taken; the first
    min(*count, capacity) entries are copied, counting goes on beyond capacity as frag_offset does (:586-592).  frag and frag_pos
    may each be NULL (both: a count-only call).  A sub-box that misses the slab gives *count = 0.
@@ -524,6 +527,60 @@ int pf_back_apply(pf_ctx *ctx, size_t count, const unsigned int *pos, size_t pos
 int pf_update_back(pf_ctx *ctx, void *products_host, size_t stride, long off_zacc, long off_group_ID);
 int pf_debug_distribute_back(int n, int x0, int nxl, const pf_peak_region *box, size_t count, const unsigned int *frag_pos,
                              const float *zacc, const int *group_id, float *zacc_out, int *group_out, size_t *stored);
+/* The redshift segments of a RECOMPUTE_DISPLACEMENTS build (the reference's default; src/fragment.c:398-430): for every segment
+   after the first, shift_all_displacements() (:832-850) copies Vel* to Vel*_prev, compute_displacements(0, 0, z) rewrites Vel*,
+   and a whole second distribute() + sort_and_organize() brings both sets into frag[] for recompute_group_velocities().  The
+   stored set and its order cannot change between segments (Fmax and the map are the same): only 24 numbers per stored particle
+   are new, and the caller holds frag_pos[].  So here the step is a gather by position from the columns.
+   pf_shift_displacements: vel12_prev := vel12, twelve more per-cell columns of PRODFLOAT laid out as the displacement columns
+   -- 48 bytes per cell, 96 with PF_FLAG_DOUBLE_PRODUCTS.  They come into being at the first shift, count into pf_device_bytes from
+   then on and are freed by pf_drop_prev or pf_destroy; when they cannot be allocated the call says how many bytes it needs and the
+   context stays as it was.  A copy on the context's stream, not an exchange of pointers: until the next pf_displacements
+   Vel == Vel_prev as in the reference, and pf_get_block / pf_distribute* may be called in between.  Refused unless
+   pf_displacements has run since the products were last reset.  pf_distribute* and pf_update_products do not know the columns.
+   pf_drop_prev: frees them (after the last segment, before the zacc / group_ID columns come into being); without columns it
+   does nothing.  pf_prev_shifts: the shifts since creation or since the last drop; 0 = there are no columns.
+   pf_gather_velocities: box = subbox.stabl, subbox.Lgwbl, subbox.safe of the sub-box the particles belong to, checked as
+   pf_map_create checks its box; a direction is periodic when len[d] == n.  Particle i lies at the sub-box position frag_pos[i] =
+   z + Lz (y + Ly x) (as pf_distribute returns it); its cell is that coordinate plus start, the start first reduced to the periodic
+   box, modulo n (src/distribute.c:806-830 WITHOUT the good_particle test of :815-817: every stored particle has velocities, the
+   boundary layer included).  It is FOUND when the x-plane of the cell lies in this rank's slab.  The found particles come back in
+   ascending i: index[j] = i, and vel24[24 j ..] = the current columns 0..11 (Vel, Vel_2LPT, Vel_3LPT_1, Vel_3LPT_2, three
+   components each) then the prev columns 0..11, as PRODFLOAT.  The slots of LPT orders the context does not compute
+   (pf_set_lpt_order) are zero, and so are the prev slots while there are no prev columns.  *found counts beyond capacity, as *count
+   of pf_distribute does; the first min(*found, capacity) entries are written; index and vel24 may each be NULL.  Duplicates in
+   frag_pos are legal.  Needs products (a sweep or pf_displacements).  NOT collective: on P ranks each rank's call finds its own
+   particles, the hit sets are disjoint and together they are all of count -- the owner of a sub-box sends frag_pos[] (4 bytes per
+   particle) to every contributor, each calls this on its own context and sends index / vel24 back.
+   order: NULL, or the caller's indices[] of sort_and_organize() / pf_distribute_sorted -- a permutation of 0 .. count - 1 in
+   ascending position.  It changes which thread serves which particle and nothing else: with it consecutive threads serve
+   z-neighbours and the column reads of a wavefront fall into few lines, while each particle's 96 bytes are written on their own;
+   without it the reads are scattered and the output leaves as contiguous words.  Output order and contents are identical either
+   way.  An order that is no permutation omits particles: their entries come back as index 0xFFFFFFFF with zero values, and
+   pf_refresh_velocities leaves their records as they are.
+   pf_refresh_velocities: the gather plus the scatter into the caller's records, done by the hand-off threads while they drain the
+   pinned pieces: frag[i] of every found particle gets the fields named by a non-negative offset in layout (the four off_Vel*;
+   off_Rmax / off_Fmax are ignored) and in prev (NULL: none -- a plain Vel* refresh; always allowed).  Every other byte of every
+   record keeps its host value, records of particles that were not found keep theirs whole.  Stride and offsets follow the rules
+   of pf_distribute's layout (multiples of four, inside the record, no overlap -- between layout and prev fields too).
+   Refused, before anything is launched: a frag_pos entry that is not below Lx Ly Lz and an order entry that is not below count
+   (checked on the host while staging; the message names the first offender); 2^31 particles or more; a bad box; a bad layout; a
+   prev that names a field before any shift ("no pf_shift_displacements yet"); no products.  When the scratch -- 4 (8 with order)
+   bytes per particle going up, 4 + 24 PRODFLOATs per found particle coming back -- cannot be allocated the call says how many
+   bytes it needs.  Transfers go through the hand-off pieces (PF_HANDOFF_CHUNK_MB).
+   pf_debug_gather_velocities: test tap without a context -- the same kernels on a caller's columns (host): planes x0 ..
+   x0 + nxl - 1 of an n^3 box, 24 columns of nxl n n values of pb = 4 or 8 bytes (current 0..11, prev 0..11); index and vel24 have
+   room for count entries. */
+typedef struct { int off_Vel_prev, off_Vel_2LPT_prev, off_Vel_3LPT_1_prev, off_Vel_3LPT_2_prev; } pf_prev_layout;  /* bytes, negative = absent */
+int pf_shift_displacements(pf_ctx *ctx);
+int pf_drop_prev(pf_ctx *ctx);
+int pf_prev_shifts(pf_ctx *ctx);
+int pf_gather_velocities(pf_ctx *ctx, const pf_peak_region *box, size_t count, const unsigned int *frag_pos, const int *order,
+                         size_t capacity, unsigned int *index, void *vel24, size_t *found);
+int pf_refresh_velocities(pf_ctx *ctx, const pf_peak_region *box, size_t count, const unsigned int *frag_pos, const int *order,
+                          void *frag, const pf_product_layout *layout, const pf_prev_layout *prev, size_t *found);
+int pf_debug_gather_velocities(int n, int x0, int nxl, int pb, const void *cols24, const pf_peak_region *box, size_t count,
+                               const unsigned int *frag_pos, const int *order, unsigned int *index, void *vel24, size_t *found);
 /* Per-particle payload of one block of the "timeless snapshot" (write_timeless_snapshot, src/write_snapshot.c:207-342)
    for this rank's slab, from the SoA columns in HBM: name = "ID  " (1 + global index as MYIDTYPE of id_bytes = 4 or 8,
    :648-664), "FMAX" float, "RMAX" int, "ZEL " / "2LPT" / "31PT" / "32PT" float[3] per particle (:700-855), and the last

@@ -52,6 +52,10 @@ class SubBox(C.Structure):
     _fields_ = [("start", C.c_int * 3), ("len", C.c_int * 3)]
 
 
+class PrevLayout(C.Structure):
+    _fields_ = [("off_Vel_prev", C.c_int), ("off_Vel_2LPT_prev", C.c_int), ("off_Vel_3LPT_1_prev", C.c_int), ("off_Vel_3LPT_2_prev", C.c_int)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -139,6 +143,15 @@ PROTOTYPES = {
     "pf_update_back": (C.c_int, [_vp, _vp, C.c_size_t, C.c_long, C.c_long]),
     "pf_debug_distribute_back": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(PeakRegion), C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_float),
                                            C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "pf_shift_displacements": (C.c_int, [_vp]),
+    "pf_drop_prev": (C.c_int, [_vp]),
+    "pf_prev_shifts": (C.c_int, [_vp]),
+    "pf_gather_velocities": (C.c_int, [_vp, C.POINTER(PeakRegion), C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_int), C.c_size_t, C.POINTER(C.c_uint), _vp,
+                                       C.POINTER(C.c_size_t)]),
+    "pf_refresh_velocities": (C.c_int, [_vp, C.POINTER(PeakRegion), C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_int), _vp, C.POINTER(ProductLayout),
+                                        C.POINTER(PrevLayout), C.POINTER(C.c_size_t)]),
+    "pf_debug_gather_velocities": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(PeakRegion), C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_int),
+                                             C.POINTER(C.c_uint), _vp, C.POINTER(C.c_size_t)]),
     "pf_set_collapse_model": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "pf_set_modified_gravity": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "pf_set_tabulated_ct": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),

@@ -199,6 +199,46 @@ def distribute_back(n: int, x0: int, nxl: int, start, length, safe, frag_pos, za
     return zout, gout, int(stored.value)
 
 
+def _order(order, count):
+    """None, or indices[] of sort_and_organize: one int32 per particle"""
+    if order is None:
+        return None, None
+    o = np.ascontiguousarray(order, dtype=np.int32).ravel()
+    if o.size != count:
+        raise ValueError(f"an order of {o.size} entries for {count} particles")
+    return o, o.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def prev_layout(off_Vel_prev=-1, off_Vel_2LPT_prev=-1, off_Vel_3LPT_1_prev=-1, off_Vel_3LPT_2_prev=-1):
+    """byte offsets of the Vel*_prev fields of a record (pf_prev_layout); negative = absent"""
+    return _lib.PrevLayout(int(off_Vel_prev), int(off_Vel_2LPT_prev), int(off_Vel_3LPT_1_prev), int(off_Vel_3LPT_2_prev))
+
+
+def debug_gather_velocities(n: int, x0: int, cols24: np.ndarray, box, frag_pos, order=None):
+    """the velocity gather of pf_gather_velocities by the device kernels without a context (pf_debug_gather_velocities): cols24 =
+    [24][nxl n n] float32 or float64, the current columns 0..11 and the prev columns 0..11 of the slab planes x0 .. x0 + nxl - 1 of
+    an n^3 box; box = (start, length, safe); the particles at the sub-box positions frag_pos; order None or indices[] of
+    sort_and_organize -> (index[found], vel24[found][24]) in ascending particle index"""
+    L = _lib.load()
+    cols = np.ascontiguousarray(cols24)
+    if cols.dtype not in (np.float32, np.float64):
+        cols = cols.astype(np.float32)
+    if cols.ndim != 2 or cols.shape[0] != 24 or cols.shape[1] % (int(n) * int(n)):
+        raise ValueError(f"columns of shape {cols.shape} for slab planes of {n} x {n} cells")
+    nxl = cols.shape[1] // (int(n) * int(n))
+    pos = np.ascontiguousarray(frag_pos, dtype=np.uint32).ravel()
+    o, op = _order(order, pos.size)
+    index = np.empty(pos.size, dtype=np.uint32)
+    vel = np.empty((pos.size, 24), dtype=cols.dtype)
+    found = C.c_size_t()
+    rg = _region(box)
+    if L.pf_debug_gather_velocities(int(n), int(x0), nxl, cols.dtype.itemsize, cols.ctypes.data_as(C.c_void_p), C.byref(rg), pos.size,
+                                    pos.ctypes.data_as(C.POINTER(C.c_uint)), op, index.ctypes.data_as(C.POINTER(C.c_uint)),
+                                    vel.ctypes.data_as(C.c_void_p), C.byref(found)):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_gather_velocities failed")
+    return index[:found.value], vel[:found.value]
+
+
 _WHICH = {"current": _lib.MAP_CURRENT, "update": _lib.MAP_UPDATE}
 
 
@@ -694,6 +734,55 @@ class Fmax:
             raise ValueError(f"records of {records.nbytes} bytes for {nc} cells")
         self._chk(self.L.pf_update_back(self.h, records.ctypes.data_as(C.c_void_p), records.nbytes // nc, int(off_zacc), int(off_group_ID)))
         return records
+
+    # -- the redshift segments of a RECOMPUTE_DISPLACEMENTS build (src/fragment.c:398-430): Vel*_prev and the refresh of frag[] ---------
+    def shift_displacements(self):
+        """shift_all_displacements() (src/fragment.c:832-850): the Vel*_prev columns := the Vel* columns; they come into being at the
+        first call (pf_shift_displacements)"""
+        self._chk(self.L.pf_shift_displacements(self.h))
+
+    def drop_prev(self):
+        """frees the Vel*_prev columns (pf_drop_prev)"""
+        self._chk(self.L.pf_drop_prev(self.h))
+
+    @property
+    def prev_shifts(self) -> int:
+        """shifts since creation or since the last drop_prev(); 0: there are no Vel*_prev columns"""
+        return int(self.L.pf_prev_shifts(self.h))
+
+    def gather_velocities(self, box, frag_pos, order=None, capacity=None):
+        """the velocities of the particles at the sub-box positions frag_pos of the sub-box box = (start, length, safe) whose cells
+        lie in this rank's slab (pf_gather_velocities) -> (index, vel24): index[j] = the particle, ascending; vel24[j] = its
+        current columns 0..11 then the prev columns 0..11, in the context's product precision.  order: None or indices[] of
+        sort_and_organize (same result; another access pattern on the device).  capacity: at most so many entries come back.
+        Not collective."""
+        pos = np.ascontiguousarray(frag_pos, dtype=np.uint32).ravel()
+        o, op = _order(order, pos.size)
+        cap = pos.size if capacity is None else int(capacity)
+        index = np.empty(cap, dtype=np.uint32)
+        vel = np.empty((cap, 24), dtype=self._zacc_dtype)
+        found = C.c_size_t()
+        rg = _region(box)
+        self._chk(self.L.pf_gather_velocities(self.h, C.byref(rg), pos.size, pos.ctypes.data_as(C.POINTER(C.c_uint)), op, cap,
+                                              index.ctypes.data_as(C.POINTER(C.c_uint)), vel.ctypes.data_as(C.c_void_p), C.byref(found)))
+        m = min(int(found.value), cap)
+        return index[:m], vel[:m]
+
+    def refresh_velocities(self, box, frag_pos, frag: np.ndarray, layout, prev=None, order=None) -> int:
+        """frag[i] of every particle of frag_pos whose cell lies in this rank's slab gets the Vel* fields named by `layout` (a
+        _lib.ProductLayout; off_Rmax / off_Fmax are ignored) and the Vel*_prev fields named by `prev` (prev_layout(); None: none)
+        from the columns; every other byte of frag keeps its value (pf_refresh_velocities) -> how many were found.  frag: the
+        caller's records, C-contiguous, layout.stride bytes each.  Not collective."""
+        pos = np.ascontiguousarray(frag_pos, dtype=np.uint32).ravel()
+        o, op = _order(order, pos.size)
+        if not (frag.flags.c_contiguous and frag.flags.writeable and frag.nbytes == pos.size * layout.stride):
+            raise ValueError(f"records of {frag.nbytes} bytes for {pos.size} particles of {layout.stride} bytes")
+        found = C.c_size_t()
+        rg = _region(box)
+        self._chk(self.L.pf_refresh_velocities(self.h, C.byref(rg), pos.size, pos.ctypes.data_as(C.POINTER(C.c_uint)), op,
+                                               frag.ctypes.data_as(C.c_void_p), C.byref(layout), C.byref(prev) if prev is not None else None,
+                                               C.byref(found)))
+        return int(found.value)
 
     def organize(self, records: np.ndarray, frag_pos: np.ndarray, layout=None):
         """sort_and_organize() (src/fragment.c:484-520) on records the caller holds (contributions of several ranks to one

@@ -160,6 +160,11 @@ struct pf_ctx {
   // block request needs them (pf_ctx_back_columns); no sweep touches them
   void *back_zacc;
   int *back_group;
+  // shift_all_displacements() (src/fragment.c:832-850): the twelve displacement columns of the segment before, laid out as vel12.
+  // Null until the first pf_shift_displacements, freed by pf_drop_prev; prev_shifts counts the shifts since then
+  void *vel12_prev;
+  int prev_shifts;
+  bool have_displacements;  // pf_displacements has written vel12 since the products were last reset
   double *partials;    // 2 * PF_NBLK
   double *scal;        // device scalars, see SC_*
   unsigned long long *hist;
@@ -531,7 +536,7 @@ extern "C" int pf_create(pf_ctx **out, const pf_config *cfg) {
   for (int i = 0; i < 6; i++) { c->B[i] = nullptr; c->B2[i] = nullptr; }
   c->blockA = nullptr; c->dk = nullptr; c->recvA = nullptr; c->tw = nullptr;
   c->blockA2 = nullptr; c->recvA2 = nullptr; c->cstream = nullptr; c->dk_full = nullptr; c->replicate = false; c->dk_full_valid = false; for (int k = 0; k < 3; k++) c->INV[0][k] = c->INV[1][k] = nullptr; c->inv_w = 0; c->inv_own[0] = c->inv_own[1] = nullptr; c->blockS = c->blockB2 = nullptr;
-  c->fmax = nullptr; c->rmax = nullptr; c->vel12 = nullptr; c->back_zacc = nullptr; c->back_group = nullptr; c->partials = nullptr; c->scal = nullptr; c->hist = nullptr; c->spl = nullptr;
+  c->fmax = nullptr; c->rmax = nullptr; c->vel12 = nullptr; c->back_zacc = nullptr; c->back_group = nullptr; c->vel12_prev = nullptr; c->prev_shifts = 0; c->have_displacements = false; c->partials = nullptr; c->scal = nullptr; c->hist = nullptr; c->spl = nullptr;
   c->gtab = nullptr; c->etab = nullptr; c->ct_block = nullptr; c->gt = nullptr; c->gt_lut = nullptr;
   memset(c->gt_ok, 0, sizeof(c->gt_ok)); memset(c->gt_err, 0, sizeof(c->gt_err));
   for (int i = 0; i < 2; i++) c->ev_x[i] = c->ev_r[i] = c->ev_y[i] = c->ev_s[i] = nullptr;
@@ -562,7 +567,7 @@ extern "C" int pf_destroy(pf_ctx *c) {
   hipFree(c->dk); hipFree(c->blockA); hipFree(c->recvA); hipFree(c->tw); hipFree(c->blockA2); hipFree(c->recvA2); hipFree(c->dk_full); hipFree(c->inv_own[0]); hipFree(c->inv_own[1]);
   for (int i = 0; i < 6; i++) hipFree(c->B[i]);
   hipFree(c->blockS); hipFree(c->blockB2);
-  hipFree(c->fmax); hipFree(c->rmax); hipFree(c->vel12); hipFree(c->back_zacc); hipFree(c->back_group); hipFree(c->partials); hipFree(c->partials_src); hipFree(c->scal); hipFree(c->hist); hipFree(c->spl); hipFree(c->gt); hipFree(c->gt_lut); hipFree(c->gtab); hipFree(c->etab); hipFree(c->ct_block); hipFree(c->W);
+  hipFree(c->fmax); hipFree(c->rmax); hipFree(c->vel12); hipFree(c->back_zacc); hipFree(c->back_group); hipFree(c->vel12_prev); hipFree(c->partials); hipFree(c->partials_src); hipFree(c->scal); hipFree(c->hist); hipFree(c->spl); hipFree(c->gt); hipFree(c->gt_lut); hipFree(c->gtab); hipFree(c->etab); hipFree(c->ct_block); hipFree(c->W);
   pf_gfft_destroy(c->fft_c2r);
   if (c->fft_r2c != c->fft_c2r) pf_gfft_destroy(c->fft_r2c);
   for (auto &e : c->evs) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
@@ -1574,6 +1579,7 @@ static int collapse_enqueue(pf_ctx *c, int ismooth, void *const H[6], hipStream_
 static int products_reset(pf_ctx *c) {
   c->vel_zero_pending = true;
   c->products_init = true;
+  c->have_displacements = false;
   return 0;
 }
 static int velocities_ready(pf_ctx *c) {
@@ -1847,6 +1853,7 @@ extern "C" int pf_displacements(pf_ctx *c, int compute_sources, int recompute_sd
       HIPCHK(c, hipMemsetAsync(velcol(c, k0), 0, (size_t)(12 - k0) * nc * (size_t)c->pb, c->stream));
     }
     c->vel_zero_pending = false;  // all twelve columns rewritten
+    c->have_displacements = true;
   }
   return 0;
 }
@@ -1988,6 +1995,45 @@ int pf_ctx_back_columns(pf_ctx *c, const char *who, void **zacc, int **group, bo
   *zacc = c->back_zacc; *group = c->back_group;
   return 0;
 }
+
+// ---- the Vel*_prev columns of a RECOMPUTE_DISPLACEMENTS build (pf_refresh.hip reads them) ----
+// shift_all_displacements() (src/fragment.c:832-850): vel12_prev := vel12 on the context's stream.  A copy, not an exchange of the
+// two pointers: until the next pf_displacements both sets hold the same values, as Vel and Vel_prev of the reference do, and
+// pf_get_block / pf_distribute* may read the current one in between.  The columns come into being here (12 PRODFLOATs per cell)
+extern "C" int pf_shift_displacements(pf_ctx *c) {
+  const char *who = "pf_shift_displacements";
+  if (!c) return pf_fail(0, "%s: null argument", who);
+  if (!c->products_init || !c->have_displacements) return pf_fail(c->rank, "%s: displacements not computed (pf_displacements must come first)", who);
+  PFCHK(c, velocities_ready(c));
+  const size_t bytes = 12 * ncell(c) * (size_t)c->pb;
+  void *p = c->vel12_prev;
+  if (!p && hipMalloc(&p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return pf_fail(c->rank, "%s: cannot allocate the %zu bytes of the Vel*_prev columns on the device (%.1f GB held by this context)", who, bytes, 1e-9 * c->dev_bytes);
+  }
+  if (hipMemcpyAsync(p, c->vel12, bytes, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    if (!c->vel12_prev) hipFree(p);
+    return pf_fail(c->rank, "%s: the copy of the columns failed", who);
+  }
+  if (!c->vel12_prev) { c->vel12_prev = p; c->dev_bytes += bytes; c->prev_shifts = 0; }
+  c->prev_shifts++;
+  return 0;
+}
+// the columns given back (after the last segment: before the zacc / group_ID columns come into being); none: nothing to do
+extern "C" int pf_drop_prev(pf_ctx *c) {
+  if (!c) return pf_fail(0, "pf_drop_prev: null argument");
+  if (c->vel12_prev) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipFree(c->vel12_prev));
+    c->vel12_prev = nullptr;
+    c->dev_bytes -= 12 * ncell(c) * (size_t)c->pb;
+  }
+  c->prev_shifts = 0;
+  return 0;
+}
+extern "C" int pf_prev_shifts(pf_ctx *c) { return c ? c->prev_shifts : -1; }
+void pf_ctx_prev_view(pf_ctx *c, const void **prev, int *shifts, int *lpt_order) { *prev = c->vel12_prev; *shifts = c->prev_shifts; *lpt_order = c->lpt_order; }
 
 // The two columns into records the caller holds -- products[i].zacc / .group_ID of a -DSNAPSHOT build --, the merge of
 // pf_update_products: the columns travel as they lie (8 bytes per cell, 12 with double products), a piece of each in one pinned
@@ -2350,6 +2396,9 @@ int pf_ctx_handoff_begin(pf_ctx *c, PfHandoffView *v) {
   for (int b = 0; b < 2; b++) { v->st[b] = h->st[b]; v->pin[b] = h->pin[b]; v->dev[b] = handoff_dev(c, b); }
   v->chunk = h->chunk;
   return 0;
+}
+void pf_ctx_host_run(pf_ctx *c, size_t count, void (*f)(void *, size_t, size_t), void *user) {
+  c->handoff->pool->run(count, [=](size_t a, size_t e) { f(user, a, e); });
 }
 void pf_ctx_host_copy(pf_ctx *c, void *dst, const void *src, size_t bytes) {
   char *d = (char *)dst; const char *s = (const char *)src;

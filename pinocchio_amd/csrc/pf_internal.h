@@ -335,6 +335,12 @@ int pf_launch_back_fill(int pb, void *zacc, int *group, size_t ncell, hipStream_
 // set to -1 / 0 on the context's stream; *fresh says that this call did it --, and a failure (message of `who` with the bytes it needs)
 // leaves the context without them, as it was
 int pf_ctx_back_columns(pf_ctx *c, const char *who, void **zacc, int **group, bool *fresh);
+// ---- pf_refresh.hip: the velocities of the stored particles of a sub-box gathered from the columns (src/fragment.c:398-430) ----
+// the Vel*_prev columns of the context (pf_api.hip: pf_shift_displacements), twelve laid out as vel12 -- null while there are none --,
+// the shifts that filled them and the LPT order whose columns are computed (pf_set_lpt_order)
+void pf_ctx_prev_view(pf_ctx *c, const void **prev, int *shifts, int *lpt_order);
+// f(user, a, b) on disjoint ranges that cover [0, count), by the host threads of the hand-off (after pf_ctx_handoff_begin)
+void pf_ctx_host_run(pf_ctx *c, size_t count, void (*f)(void *user, size_t a, size_t b), void *user);
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);
