@@ -581,6 +581,59 @@ int pf_refresh_velocities(pf_ctx *ctx, const pf_peak_region *box, size_t count, 
                           void *frag, const pf_product_layout *layout, const pf_prev_layout *prev, size_t *found);
 int pf_debug_gather_velocities(int n, int x0, int nxl, int pb, const void *cols24, const pf_peak_region *box, size_t count,
                                const unsigned int *frag_pos, const int *order, unsigned int *index, void *vel24, size_t *found);
+/* The group velocities of a segment on the device: recompute_group_velocities() (src/fragment.c:852-909), the line behind the
+   re-distribution, is a segmented sum of the same 24 columns over the particles of every group, and the only consumer of most of
+   what pf_refresh_velocities brings back -- once a particle has joined a group the reference reads its frag[].Vel* no more
+   (INTEGRATION.md has the argument).  So a segment needs the frag[] fields of the particles that are still loose and the group
+   means; the grouped particles' 96 bytes need not cross the link.
+   Which particles count: box, frag_pos and FOUND mean exactly what they mean for pf_gather_velocities (the cell of the position
+   lies in this rank's slab; no good_particle test; duplicates are legal and count twice).  group_id points at the first
+   particle's int, group_stride is the byte distance to the next (the reference's packed group_ID[]: 4; or a field of a record).
+   Particle i is COUNTED when it is found and group_id[i] >= first_group -- the caller passes FILAMENT + 1 = 2 --, and LOOSE when it
+   is found and group_id[i] < first_group.
+   pf_group_velocity_sums: the groups with at least one counted particle on this rank in ascending group ID: group[j] the ID,
+   npart[j] the number of counted particles, sum24[24 j + k] the fp64 sum of column k over them -- columns 0..11 current, 12..23
+   prev, in the order of vel24; a column is zero where the LPT order or the prev columns are absent; with PF_FLAG_DOUBLE_PRODUCTS
+   the columns are fp64 already.  The sums are deterministic: they depend on the set of (group, cell, value) alone, not on the order
+   of the particles nor on the schedule (sorted keys, a fixed tree of additions, no floating-point atomics); the error of a sum is
+   within npart 2^-53 sum|v|.  *groups_found counts beyond capacity, as *found does elsewhere; the first min(*groups_found,
+   capacity) entries are written; *particles_found = the counted particles; each output pointer may be NULL.  NOT collective, like
+   pf_gather_velocities: with several contributors the owner adds npart and sum24 of equal IDs and divides.  Refused before any
+   launch, the first offender named: a negative group_id; a frag_pos entry not below Lx Ly Lz; 2^31 particles or more; a stride
+   that is no multiple of 4; a bad box; no products; a slab of more than 2^32 cells.  Scratch that cannot be allocated is reported
+   with its size: 8 bytes per particle going up, then per counted particle 16 bytes of keys plus the sort's own, and 200 bytes per
+   group.
+   pf_refresh_segment: the whole step of fragment.c:416-427 for ONE contributor that keeps frag[] and groups[].  The loose
+   particles get their frag[] fields exactly as pf_refresh_velocities writes them (layout, prev, order as there); every other byte,
+   and every record of a grouped or not-found particle, keeps its value.  Every group g in [first_group, ngroups] with npart > 0
+   gets (PRODFLOAT)(sum / npart) in the fields gl names, in record g of groups (ngroups + 1 records of gl->stride bytes, as the
+   reference's groups[0 .. ngroups]); groups without particles keep their bytes, and so does every byte gl does not name.  Where
+   gl->off_Mass >= 0, *mass_mismatch counts the groups whose int at that offset differs from npart: reported, not refused -- the
+   caller decides.  A group ID above ngroups is refused (named, before any launch).  frag == NULL skips the loose half, groups ==
+   NULL the group half.  *loose / *grouped: the particles of either class.  The layouts follow the rules of pf_distribute's layout
+   (multiples of four, inside the record, no overlap).  The means are plain means: the reference zeroes Vel_prev twice and
+   Vel_2LPT_prev never (src/fragment.c:863), so ITS Vel_2LPT_prev is (old value + sum) / Mass; a caller who wants that literally
+   has the sums of pf_group_velocity_sums.
+   pf_debug_group_velocity_sums: test tap without a context -- the same kernels on a caller's columns (host), as
+   pf_debug_gather_velocities; group, npart and sum24 have room for count entries.
+   pf_debug_groupvel_times: with PF_GROUPVEL_TIMES=1 in the environment every call above measures its stages between events on its
+   stream (one more synchronisation per call); ms3 = the device ms of the last call's keys + sort, head flags + scan, and
+   reduce + fold.  Zeros otherwise.  For profiles/tools/groupvel_time.py. */
+typedef struct { size_t stride; long off_Mass, off_Vel, off_Vel_2LPT, off_Vel_3LPT_1, off_Vel_3LPT_2,
+                 off_Vel_prev, off_Vel_2LPT_prev, off_Vel_3LPT_1_prev, off_Vel_3LPT_2_prev; } pf_group_layout;  /* bytes, negative = absent */
+int pf_group_velocity_sums(pf_ctx *ctx, const pf_peak_region *box, size_t count, const unsigned int *frag_pos,
+                           const int *group_id, size_t group_stride, int first_group,
+                           size_t capacity, int *group, unsigned int *npart, double *sum24,
+                           size_t *groups_found, size_t *particles_found);
+int pf_refresh_segment(pf_ctx *ctx, const pf_peak_region *box, size_t count, const unsigned int *frag_pos, const int *order,
+                       const int *group_id, size_t group_stride, int first_group,
+                       void *frag, const pf_product_layout *layout, const pf_prev_layout *prev,
+                       void *groups, size_t ngroups, const pf_group_layout *gl,
+                       size_t *loose, size_t *grouped, size_t *mass_mismatch);
+int pf_debug_group_velocity_sums(int n, int x0, int nxl, int pb, const void *cols24, const pf_peak_region *box, size_t count,
+                                 const unsigned int *frag_pos, const int *group_id, int first_group,
+                                 int *group, unsigned int *npart, double *sum24, size_t *groups_found, size_t *particles_found);
+int pf_debug_groupvel_times(double *ms3);
 /* Per-particle payload of one block of the "timeless snapshot" (write_timeless_snapshot, src/write_snapshot.c:207-342)
    for this rank's slab, from the SoA columns in HBM: name = "ID  " (1 + global index as MYIDTYPE of id_bytes = 4 or 8,
    :648-664), "FMAX" float, "RMAX" int, "ZEL " / "2LPT" / "31PT" / "32PT" float[3] per particle (:700-855), and the last

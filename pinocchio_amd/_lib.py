@@ -56,6 +56,12 @@ class PrevLayout(C.Structure):
     _fields_ = [("off_Vel_prev", C.c_int), ("off_Vel_2LPT_prev", C.c_int), ("off_Vel_3LPT_1_prev", C.c_int), ("off_Vel_3LPT_2_prev", C.c_int)]
 
 
+class GroupLayout(C.Structure):
+    _fields_ = [("stride", C.c_size_t), ("off_Mass", C.c_long), ("off_Vel", C.c_long), ("off_Vel_2LPT", C.c_long), ("off_Vel_3LPT_1", C.c_long),
+                ("off_Vel_3LPT_2", C.c_long), ("off_Vel_prev", C.c_long), ("off_Vel_2LPT_prev", C.c_long), ("off_Vel_3LPT_1_prev", C.c_long),
+                ("off_Vel_3LPT_2_prev", C.c_long)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -152,6 +158,15 @@ PROTOTYPES = {
                                         C.POINTER(PrevLayout), C.POINTER(C.c_size_t)]),
     "pf_debug_gather_velocities": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(PeakRegion), C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_int),
                                              C.POINTER(C.c_uint), _vp, C.POINTER(C.c_size_t)]),
+    "pf_group_velocity_sums": (C.c_int, [_vp, C.POINTER(PeakRegion), C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_int), C.c_size_t, C.c_int, C.c_size_t,
+                                         C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_double), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "pf_refresh_segment": (C.c_int, [_vp, C.POINTER(PeakRegion), C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_size_t, C.c_int,
+                                     _vp, C.POINTER(ProductLayout), C.POINTER(PrevLayout), _vp, C.c_size_t, C.POINTER(GroupLayout), C.POINTER(C.c_size_t),
+                                     C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "pf_debug_group_velocity_sums": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(PeakRegion), C.c_size_t, C.POINTER(C.c_uint),
+                                               C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_double),
+                                               C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "pf_debug_groupvel_times": (C.c_int, [C.POINTER(C.c_double)]),
     "pf_set_collapse_model": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "pf_set_modified_gravity": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "pf_set_tabulated_ct": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),

@@ -239,6 +239,65 @@ def debug_gather_velocities(n: int, x0: int, cols24: np.ndarray, box, frag_pos, 
     return index[:found.value], vel[:found.value]
 
 
+def group_layout(stride, off_Mass=-1, off_Vel=-1, off_Vel_2LPT=-1, off_Vel_3LPT_1=-1, off_Vel_3LPT_2=-1, off_Vel_prev=-1, off_Vel_2LPT_prev=-1,
+                 off_Vel_3LPT_1_prev=-1, off_Vel_3LPT_2_prev=-1):
+    """byte offsets of Mass and the Vel* / Vel*_prev fields of a group record (pf_group_layout); negative = absent"""
+    return _lib.GroupLayout(int(stride), int(off_Mass), int(off_Vel), int(off_Vel_2LPT), int(off_Vel_3LPT_1), int(off_Vel_3LPT_2), int(off_Vel_prev),
+                            int(off_Vel_2LPT_prev), int(off_Vel_3LPT_1_prev), int(off_Vel_3LPT_2_prev))
+
+
+def _group_ids(group_id, count):
+    """group_ID of every particle as the calls take it: (array kept alive, pointer to the first int, byte stride).  A packed int32
+    array, or a strided int32 view of a field of the caller's records (read in place)"""
+    g = np.asarray(group_id)
+    if g.dtype != np.int32 or g.ndim != 1:
+        g = np.ascontiguousarray(g, dtype=np.int32).ravel()
+    if g.size != count:
+        raise ValueError(f"{g.size} group IDs for {count} particles")
+    stride = g.strides[0] if g.size > 1 else 4
+    if stride <= 0:
+        g = np.ascontiguousarray(g)
+        stride = 4
+    return g, C.cast(C.c_void_p(g.ctypes.data), C.POINTER(C.c_int)), stride
+
+
+def debug_group_velocity_sums(n: int, x0: int, cols24: np.ndarray, box, frag_pos, group_id, first_group=2):
+    """the group sums of pf_group_velocity_sums by the device kernels without a context (pf_debug_group_velocity_sums): cols24 =
+    [24][nxl n n] float32 or float64 as for debug_gather_velocities; the particles at the sub-box positions frag_pos with the group
+    IDs group_id -> (group[G], npart[G], sum24[G][24] float64, particles counted), the groups in ascending ID"""
+    L = _lib.load()
+    cols = np.ascontiguousarray(cols24)
+    if cols.dtype not in (np.float32, np.float64):
+        cols = cols.astype(np.float32)
+    if cols.ndim != 2 or cols.shape[0] != 24 or cols.shape[1] % (int(n) * int(n)):
+        raise ValueError(f"columns of shape {cols.shape} for slab planes of {n} x {n} cells")
+    nxl = cols.shape[1] // (int(n) * int(n))
+    pos = np.ascontiguousarray(frag_pos, dtype=np.uint32).ravel()
+    g = np.ascontiguousarray(group_id, dtype=np.int32).ravel()
+    if g.size != pos.size:
+        raise ValueError(f"{g.size} group IDs for {pos.size} particles")
+    group = np.empty(pos.size, dtype=np.int32)
+    npart = np.empty(pos.size, dtype=np.uint32)
+    sums = np.empty((pos.size, 24), dtype=np.float64)
+    ng, npc = C.c_size_t(), C.c_size_t()
+    rg = _region(box)
+    if L.pf_debug_group_velocity_sums(int(n), int(x0), nxl, cols.dtype.itemsize, cols.ctypes.data_as(C.c_void_p), C.byref(rg), pos.size,
+                                      pos.ctypes.data_as(C.POINTER(C.c_uint)), g.ctypes.data_as(C.POINTER(C.c_int)), int(first_group),
+                                      group.ctypes.data_as(C.POINTER(C.c_int)), npart.ctypes.data_as(C.POINTER(C.c_uint)),
+                                      sums.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ng), C.byref(npc)):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_group_velocity_sums failed")
+    return group[:ng.value], npart[:ng.value], sums[:ng.value], int(npc.value)
+
+
+def debug_groupvel_times():
+    """device ms of the last group-velocity call's stages (keys + sort, head flags + scan, reduce + fold) when PF_GROUPVEL_TIMES=1 is
+    set in the environment, zeros otherwise (pf_debug_groupvel_times)"""
+    L = _lib.load()
+    ms = (C.c_double * 3)()
+    L.pf_debug_groupvel_times(ms)
+    return {"sort_ms": ms[0], "heads_ms": ms[1], "reduce_ms": ms[2]}
+
+
 _WHICH = {"current": _lib.MAP_CURRENT, "update": _lib.MAP_UPDATE}
 
 
@@ -783,6 +842,48 @@ class Fmax:
                                                frag.ctypes.data_as(C.c_void_p), C.byref(layout), C.byref(prev) if prev is not None else None,
                                                C.byref(found)))
         return int(found.value)
+
+    def group_velocity_sums(self, box, frag_pos, group_id, first_group=2, capacity=None):
+        """the fp64 sums of the 24 velocity columns over the particles of every group (pf_group_velocity_sums): of the particles at
+        the sub-box positions frag_pos whose cells lie in this rank's slab, those with group_id >= first_group (FILAMENT + 1) ->
+        (group, npart, sum24[G][24], groups_found, particles_found), the groups in ascending ID; capacity: at most so many groups
+        come back (groups_found counts on).  group_id: int32, packed or a strided view of a field of the records.  Not collective:
+        several contributors' npart and sum24 of equal IDs add up."""
+        pos = np.ascontiguousarray(frag_pos, dtype=np.uint32).ravel()
+        g, gp, gs = _group_ids(group_id, pos.size)
+        cap = pos.size if capacity is None else int(capacity)
+        group = np.empty(cap, dtype=np.int32)
+        npart = np.empty(cap, dtype=np.uint32)
+        sums = np.empty((cap, 24), dtype=np.float64)
+        ng, npc = C.c_size_t(), C.c_size_t()
+        rg = _region(box)
+        self._chk(self.L.pf_group_velocity_sums(self.h, C.byref(rg), pos.size, pos.ctypes.data_as(C.POINTER(C.c_uint)), gp, gs, int(first_group), cap,
+                                                group.ctypes.data_as(C.POINTER(C.c_int)), npart.ctypes.data_as(C.POINTER(C.c_uint)),
+                                                sums.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ng), C.byref(npc)))
+        m = min(int(ng.value), cap)
+        return group[:m], npart[:m], sums[:m], int(ng.value), int(npc.value)
+
+    def refresh_segment(self, box, frag_pos, group_id, frag=None, layout=None, prev=None, groups=None, ngroups=0, group_layout=None, order=None,
+                        first_group=2):
+        """the step of fragment.c:416-427 in one call (pf_refresh_segment): the records frag[i] of the LOOSE particles (found,
+        group_id < first_group) get their Vel* / Vel*_prev fields as refresh_velocities writes them; record g of `groups`
+        (ngroups + 1 records of group_layout.stride bytes) of every group with counted particles gets the means in the fields
+        group_layout names.  frag None skips the first half, groups None the second -> (loose, grouped, mass_mismatch)."""
+        pos = np.ascontiguousarray(frag_pos, dtype=np.uint32).ravel()
+        o, op = _order(order, pos.size)
+        g, gp, gs = _group_ids(group_id, pos.size)
+        if frag is not None and not (frag.flags.c_contiguous and frag.flags.writeable and frag.nbytes == pos.size * layout.stride):
+            raise ValueError(f"records of {frag.nbytes} bytes for {pos.size} particles of {layout.stride} bytes")
+        if groups is not None and not (groups.flags.c_contiguous and groups.flags.writeable and groups.nbytes == (int(ngroups) + 1) * group_layout.stride):
+            raise ValueError(f"group records of {groups.nbytes} bytes for groups 0 .. {ngroups} of {group_layout.stride} bytes")
+        loose, grouped, mism = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        rg = _region(box)
+        self._chk(self.L.pf_refresh_segment(self.h, C.byref(rg), pos.size, pos.ctypes.data_as(C.POINTER(C.c_uint)), op, gp, gs, int(first_group),
+                                            frag.ctypes.data_as(C.c_void_p) if frag is not None else None, C.byref(layout) if layout is not None else None,
+                                            C.byref(prev) if prev is not None else None, groups.ctypes.data_as(C.c_void_p) if groups is not None else None,
+                                            int(ngroups), C.byref(group_layout) if group_layout is not None else None, C.byref(loose), C.byref(grouped),
+                                            C.byref(mism)))
+        return int(loose.value), int(grouped.value), int(mism.value)
 
     def organize(self, records: np.ndarray, frag_pos: np.ndarray, layout=None):
         """sort_and_organize() (src/fragment.c:484-520) on records the caller holds (contributions of several ranks to one

@@ -341,6 +341,26 @@ int pf_ctx_back_columns(pf_ctx *c, const char *who, void **zacc, int **group, bo
 void pf_ctx_prev_view(pf_ctx *c, const void **prev, int *shifts, int *lpt_order);
 // f(user, a, b) on disjoint ranges that cover [0, count), by the host threads of the hand-off (after pf_ctx_handoff_begin)
 void pf_ctx_host_run(pf_ctx *c, size_t count, void (*f)(void *user, size_t a, size_t b), void *user);
+// what pf_groupvel.hip shares with it.  The columns as 4-byte words: cur / prev = twelve columns of ncell PRODFLOATs each (prev null:
+// its slots read zero); columns kmax .. 11 of either set read zero (the LPT orders the context does not compute)
+struct PfRefreshCols { const unsigned int *cur, *prev; size_t ncell; int kmax; };
+// what a call holds on the device beside the columns: masks / counts / offs are the ballots, block counts and their scan of whatever
+// flag pass filled them (k_refresh_flag: found; k_groupvel_flag: found and loose)
+struct PfRefreshScratch { unsigned int *pos; int *order; unsigned long long *masks, *offs; unsigned int *counts; unsigned int *index; void *vel; };
+struct PfRefreshFields { int nf; int off[8], slot[8]; };
+struct PfBackBox;
+void pf_refresh_release(PfRefreshScratch *s);
+size_t pf_refresh_blocks(size_t count);
+size_t pf_refresh_in_bytes(size_t count, bool with_order);
+int pf_refresh_alloc_in(PfRefreshScratch *s, size_t count, bool with_order);
+int pf_refresh_alloc_out(PfRefreshScratch *s, size_t m, int pb, bool want_index, bool want_vel);
+int pf_refresh_scan(const unsigned int *counts, size_t nblocks, unsigned long long *offs, hipStream_t st);   // k_refresh_scan
+int pf_refresh_gather(int pb, const PfBackBox &b, size_t count, const PfRefreshScratch &s, const PfRefreshCols &cols, unsigned long long cap, hipStream_t st);
+int pf_refresh_box(const char *who, int rank, int n, int x0, int nxl, const pf_peak_region *box, PfBackBox *b, unsigned long long *cells);
+size_t pf_refresh_first_bad(const unsigned int *a, size_t upto, unsigned long long limit);
+int pf_refresh_fields(const char *who, int rank, int pb, int shifts, const pf_product_layout *l, const pf_prev_layout *p, PfRefreshFields *f);
+int pf_refresh_to_records(pf_ctx *c, const PfCtxView &v, const char *who, const PfRefreshScratch &s, size_t m, size_t count, void *frag, size_t stride,
+                          const PfRefreshFields &f);
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);

@@ -81,10 +81,7 @@ __global__ void __launch_bounds__(1024) k_refresh_scan(const unsigned int *__res
   if (tid == 0) offs[nblocks] = carry;
 }
 
-// the columns as 4-byte words: cur / prev = twelve columns of ncell PRODFLOATs each (prev null: its slots read zero); columns
-// kmax .. 11 of either set read zero (the LPT orders the context does not compute)
-struct PfRefreshCols { const unsigned int *cur, *prev; size_t ncell; int kmax; };
-
+// the columns as 4-byte words: PfRefreshCols (pf_internal.h)
 // word w (0 .. 24 WPE - 1) of the output of the particle whose cell is addr: value k = w / WPE -- current column k, or prev column
 // k - 12 --, half h = w % WPE of it
 template <int WPE>
@@ -161,8 +158,7 @@ __global__ void __launch_bounds__(PF_REFRESH_BLOCK) k_refresh_gather(PfBackBox b
     if (e__ != hipSuccess) return pf_fail(task, "%s: %s failed: %s", who, #call, hipGetErrorString(e__));             \
   } while (0)
 
-// what a call holds on the device beside the columns
-struct PfRefreshScratch { unsigned int *pos; int *order; unsigned long long *masks, *offs; unsigned int *counts; unsigned int *index; void *vel; };
+// what a call holds on the device beside the columns: PfRefreshScratch (pf_internal.h)
 static void refresh_release(PfRefreshScratch *s) {
   hipFree(s->pos); hipFree(s->order); hipFree(s->masks); hipFree(s->offs); hipFree(s->counts); hipFree(s->index); hipFree(s->vel);
   memset(s, 0, sizeof(*s));
@@ -228,8 +224,7 @@ static size_t refresh_first_bad(const unsigned int *a, size_t upto, unsigned lon
 }
 
 // the fields of a record the refresh writes: slot s = 0..3 the current Vel, Vel_2LPT, Vel_3LPT_1, Vel_3LPT_2, 4..7 their *_prev;
-// three PRODFLOATs each, values 3 s .. 3 s + 2 of a particle's 24
-struct PfRefreshFields { int nf; int off[8], slot[8]; };
+// three PRODFLOATs each, values 3 s .. 3 s + 2 of a particle's 24 (PfRefreshFields, pf_internal.h)
 static int refresh_fields(const char *who, int rank, int pb, int shifts, const pf_product_layout *l, const pf_prev_layout *p, PfRefreshFields *f) {
   f->nf = 0;
   if (l->stride < 4 || l->stride % 4 || l->stride / 4 > 0x7fffffffu)
@@ -321,6 +316,39 @@ static void refresh_scatter(void *user, size_t a, size_t e) {
   }
 }
 
+// the first m entries of s.index / s.vel into the caller's records: index and values of a piece in one pinned buffer, the values
+// behind the indices (8-byte aligned); the host threads scatter the named fields into the records while the next piece travels
+static int refresh_to_records(pf_ctx *c, const PfCtxView &v, const char *who, const PfRefreshScratch &s, size_t m, size_t count, void *frag, size_t stride,
+                              const PfRefreshFields &f) {
+  PfScopedTimer pt(c, 1);
+  PfHandoffView h;
+  if (pf_ctx_handoff_begin(c, &h)) return 1;
+  const size_t pb = (size_t)v.pb, vb = 24 * pb;
+  const size_t per = (h.chunk / (4 + vb)) & ~(size_t)1;
+  if (!per) return pf_fail(v.rank, "%s: a particle does not fit the staging pieces", who);
+  const size_t np = (m + per - 1) / per;
+  auto issue = [&](size_t k) -> int {
+    const int q = (int)(k & 1);
+    const size_t first = k * per, cnt = m - first < per ? m - first : per;
+    REFHIP(v.rank, who, hipMemcpyAsync(h.pin[q], s.index + first, cnt * 4, hipMemcpyDeviceToHost, h.st[q]));
+    REFHIP(v.rank, who, hipMemcpyAsync(h.pin[q] + per * 4, (const char *)s.vel + first * vb, cnt * vb, hipMemcpyDeviceToHost, h.st[q]));
+    return 0;
+  };
+  if (issue(0)) return 1;
+  for (size_t k = 0; k < np; k++) {
+    if (k + 1 < np && issue(k + 1)) return 1;
+    const int q = (int)(k & 1);
+    REFHIP(v.rank, who, hipStreamSynchronize(h.st[q]));
+    const size_t first = k * per, cnt = m - first < per ? m - first : per;
+    const unsigned int *idx = (const unsigned int *)h.pin[q];
+    const char *val = h.pin[q] + per * 4;
+    char *rec = (char *)frag;
+    RefreshScatter job{idx, val, rec, stride, vb, pb, count, f};
+    pf_ctx_host_run(c, cnt, refresh_scatter, &job);
+  }
+  return 0;
+}
+
 // -------------------------------------------------------------------------------------------------------- entry points ----
 extern "C" int pf_gather_velocities(pf_ctx *c, const pf_peak_region *box, size_t count, const unsigned int *frag_pos, const int *order, size_t capacity,
                                     unsigned int *index, void *vel24, size_t *found) {
@@ -357,35 +385,7 @@ extern "C" int pf_refresh_velocities(pf_ctx *c, const pf_peak_region *box, size_
   if (refresh_run(c, v, who, box, count, frag_pos, order, count, f.nf > 0, f.nf > 0, &s, &nfound, &m)) return 1;
   if (found) *found = nfound;
   if (!m || !f.nf) return 0;
-  // index and values of a piece in one pinned buffer, the values behind the indices (8-byte aligned); the host threads scatter the
-  // named fields into the records while the next piece travels
-  PfScopedTimer pt(c, 1);
-  PfHandoffView h;
-  if (pf_ctx_handoff_begin(c, &h)) return 1;
-  const size_t pb = (size_t)v.pb, vb = 24 * pb, stride = layout->stride;
-  const size_t per = (h.chunk / (4 + vb)) & ~(size_t)1;
-  if (!per) return pf_fail(v.rank, "%s: a particle does not fit the staging pieces", who);
-  const size_t np = (m + per - 1) / per;
-  auto issue = [&](size_t k) -> int {
-    const int q = (int)(k & 1);
-    const size_t first = k * per, cnt = m - first < per ? m - first : per;
-    REFHIP(v.rank, who, hipMemcpyAsync(h.pin[q], s.index + first, cnt * 4, hipMemcpyDeviceToHost, h.st[q]));
-    REFHIP(v.rank, who, hipMemcpyAsync(h.pin[q] + per * 4, (const char *)s.vel + first * vb, cnt * vb, hipMemcpyDeviceToHost, h.st[q]));
-    return 0;
-  };
-  if (issue(0)) return 1;
-  for (size_t k = 0; k < np; k++) {
-    if (k + 1 < np && issue(k + 1)) return 1;
-    const int q = (int)(k & 1);
-    REFHIP(v.rank, who, hipStreamSynchronize(h.st[q]));
-    const size_t first = k * per, cnt = m - first < per ? m - first : per;
-    const unsigned int *idx = (const unsigned int *)h.pin[q];
-    const char *val = h.pin[q] + per * 4;
-    char *rec = (char *)frag;
-    RefreshScatter job{idx, val, rec, stride, vb, pb, count, f};
-    pf_ctx_host_run(c, cnt, refresh_scatter, &job);
-  }
-  return 0;
+  return refresh_to_records(c, v, who, s, m, count, frag, layout->stride, f);
 }
 
 // test tap without a context: the same kernels on a caller's columns, on the default stream
@@ -431,4 +431,29 @@ extern "C" int pf_debug_gather_velocities(int n, int x0, int nxl, int pb, const 
   }
   if (found) *found = (size_t)h;
   return 0;
+}
+
+// ---- what pf_groupvel.hip uses of the above (pf_internal.h) ----
+void pf_refresh_release(PfRefreshScratch *s) { refresh_release(s); }
+size_t pf_refresh_blocks(size_t count) { return refresh_blocks(count); }
+size_t pf_refresh_in_bytes(size_t count, bool with_order) { return refresh_in_bytes(count, with_order); }
+int pf_refresh_alloc_in(PfRefreshScratch *s, size_t count, bool with_order) { return refresh_alloc_in(s, count, with_order); }
+int pf_refresh_alloc_out(PfRefreshScratch *s, size_t m, int pb, bool want_index, bool want_vel) { return refresh_alloc_out(s, m, pb, want_index, want_vel); }
+int pf_refresh_scan(const unsigned int *counts, size_t nblocks, unsigned long long *offs, hipStream_t st) {
+  hipLaunchKernelGGL(k_refresh_scan, dim3(1), dim3(1024), 0, st, counts, (unsigned long long)nblocks, offs);
+  return hipGetLastError() != hipSuccess;
+}
+int pf_refresh_gather(int pb, const PfBackBox &b, size_t count, const PfRefreshScratch &s, const PfRefreshCols &cols, unsigned long long cap, hipStream_t st) {
+  return refresh_gather(pb, b, count, s, cols, cap, st);
+}
+int pf_refresh_box(const char *who, int rank, int n, int x0, int nxl, const pf_peak_region *box, PfBackBox *b, unsigned long long *cells) {
+  return refresh_box(who, rank, n, x0, nxl, box, b, cells);
+}
+size_t pf_refresh_first_bad(const unsigned int *a, size_t upto, unsigned long long limit) { return refresh_first_bad(a, upto, limit); }
+int pf_refresh_fields(const char *who, int rank, int pb, int shifts, const pf_product_layout *l, const pf_prev_layout *p, PfRefreshFields *f) {
+  return refresh_fields(who, rank, pb, shifts, l, p, f);
+}
+int pf_refresh_to_records(pf_ctx *c, const PfCtxView &v, const char *who, const PfRefreshScratch &s, size_t m, size_t count, void *frag, size_t stride,
+                          const PfRefreshFields &f) {
+  return refresh_to_records(c, v, who, s, m, count, frag, stride, f);
 }
