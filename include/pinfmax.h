@@ -634,6 +634,66 @@ int pf_debug_group_velocity_sums(int n, int x0, int nxl, int pb, const void *col
                                  const unsigned int *frag_pos, const int *group_id, int first_group,
                                  int *group, unsigned int *npart, double *sum24, size_t *groups_found, size_t *particles_found);
 int pf_debug_groupvel_times(double *ms3);
+/* --- the past-light-cone test of build_groups() on the device (src/build_groups.c:356-448 and :783-868, a -DPLC build) ---
+   For every good, massive group and every replication of the box the reference asks whether the group crossed the observer's
+   light cone between a lower F and its Flast, finds the crossing F with a root finder and stores a plcgroup_data record.  Here
+   the position of a group and the comoving distance at the two ends of its interval are computed once per group and serve every
+   replication; only the crossing pairs reach the root finder (INTEGRATION.md has the two call sites).
+   pf_plc_set_cosmology: the reference's splines the test reads, all on the abscissa x = -log10(1 + z) (n knots, increasing, 3 to
+   512), evaluated as my_spline_eval does (src/cosmo.c:2016-2027): GSL's natural cubic spline inside, linear extrapolation outside.
+   comvdist = SP_COMVDIST; grow[f] / fomega[f], f = 0..3 for the orders 1, 2, 31, 32: nk tables of n values each, the growth
+   tables as log10 (SP_GROW31 positive: the minus sign of cosmo.c:1810 is applied here).  nk = 1 is the scale-independent build
+   and reads k_for_GM; nk > 1 (at most 32) is -DSCALE_DEPENDENT with the bins log10 k = logkmin + j deltalogk, interpolated as
+   InterpolateGrowth does (cosmo.c:1728-1755), and reads Smoothing.Rad_GM[0], Nsmooth >= 2 and k_GM_displ[Nsmooth], from which
+   set_obj takes a group's own k (:1361-1375).  hubble: Hubble(z) at the same knots -- set_obj_vel's factor (:1449) reads this
+   table where the reference calls its closed form.
+   pf_plc_set_geometry: plc.center, the three versors, PLCAperture (degrees), Fstop, InterPartDist, GSglobal, the replications
+   (src/pinocchio.h:412-416; F1, F2 are PRODFLOATs there and are rounded to PRODFLOAT here), and LastzForPLC, delta_z, nzbins of
+   the n(z) histogram.  Both calls work on a context that has run no sweep, replace what an earlier call set, and refuse null
+   pointers, knots that do not increase, nk or nsmooth out of range and zero replications.  What they keep on the device (the tables,
+   32 bytes per replication) is freed by pf_destroy and is not counted in pf_device_bytes.
+   pf_plc_cross: `ncand` records of `gl->stride` bytes at `groups`, each a group state: Mass (int), Pos (PRODFLOAT[3]), name
+   (unsigned long long), Flast (PRODFLOAT), good and point (int), and the velocities of pf_group_layout; a negative offset = absent
+   (velocities read zero; an absent good or point passes; Mass, Pos and Flast must be there).  The host threads pack what goes up:
+   29 PRODFLOATs, Mass and one byte -- 121 bytes per candidate (237 with PF_FLAG_DOUBLE_PRODUCTS).  A candidate is tested when point >= 0 && good && Mass >= min_mass.
+   seg: myseg, z_seg = ScaleDep.z[myseg], z_prev = ScaleDep.z[myseg - 1] (read when myseg >= 1): the weights of set_weight
+   (:1411-1444); use_v31 = 0 reproduces src/build_groups.c:1588 as written (w31 times v32), 1 the line as meant.  box->start is
+   subbox.stabl; periodic wrapping is off, as the reference switches it off around the test.  The displacement order is
+   ORDER_FOR_CATALOG = 3, capped by pf_set_lpt_order.
+   mode PF_PLC_LAST_CHECK: the lower end of every interval is Fstop (f_lo ignored), replication r is tried when Flast > F2 (:819).
+   mode PF_PLC_EVENTS: the lower end of candidate i is the PRODFLOAT at f_lo + i f_lo_stride, r is tried when !(F_lo > F1 ||
+   Flast < F2) (:394-395) -- for a host that logs (group state, Flast, F) at every touch and flushes the log in batches.
+   A tried pair with bb = condition_PLC(F_lo) == 0 is stored at F_lo; with bb > 0 and condition_PLC(Flast) < 0 at the root in
+   between: a PRODFLOAT F in [F_lo, Flast] with |condition_PLC(F)| < 1e-2 InterPartDist, the stopping rule of find_brent (:1865),
+   found by a bracketing method of our own within 100 iterations.  A pair that does not get there counts in *unconverged and is
+   not stored.  Storing is store_PLC (:1764-1822): the aperture test, then z = F - 1, Mass, name, x[3], v[3] into the fields `ol`
+   names (negative = absent) of record j of plcgroups.
+   Records come in ascending (candidate, replication) order and are the same from run to run (flags, scans, compactions; no atomic
+   decides an order).  *count is the number found; the first min(*count, capacity) are written.  cand_of / rep_of (optional) name
+   the pair of every written record.  nz (optional, nzbins doubles) gets +1.0 per written record in bin (int)((z - LastzForPLC) /
+   delta_z), the top edge folded in (:1813-1816); a bin outside the histogram is skipped.
+   pf_debug_plc_times: with PF_PLC_TIMES=1 in the environment pf_plc_cross measures its device part between two events (one more
+   synchronisation); ms2 = the device ms of the last call's candidate passes and of its root + store passes.  Zeros otherwise. */
+#define PF_PLC_LAST_CHECK 0
+#define PF_PLC_EVENTS 1
+typedef struct { int n; const double *x, *comvdist, *hubble; int nk; const double *grow[4], *fomega[4];
+                 double logkmin, deltalogk, k_for_GM, rad_gm0; int nsmooth; const double *k_gm_displ; } pf_plc_cosmology;
+typedef struct { int i, j, k; double F1, F2; } pf_plc_replication;
+typedef struct { double center[3], xvers[3], yvers[3], zvers[3], aperture, Fstop, InterPartDist; long long GSglobal[3];
+                 size_t nrep; const pf_plc_replication *repls; double LastzForPLC, delta_z; int nzbins; } pf_plc_geometry;
+typedef struct { int myseg, use_v31; double z_seg, z_prev; } pf_plc_segment;
+typedef struct { size_t stride; long off_Mass, off_Pos, off_name, off_Flast, off_good, off_point, off_Vel, off_Vel_2LPT, off_Vel_3LPT_1, off_Vel_3LPT_2,
+                 off_Vel_prev, off_Vel_2LPT_prev, off_Vel_3LPT_1_prev, off_Vel_3LPT_2_prev; } pf_plc_group_layout;  /* bytes, negative = absent */
+typedef struct { size_t stride; long off_Mass, off_name, off_z, off_x, off_v; } pf_plc_out_layout;
+int pf_plc_set_cosmology(pf_ctx *ctx, const pf_plc_cosmology *cosmo);
+int pf_plc_set_geometry(pf_ctx *ctx, const pf_plc_geometry *geom);
+int pf_plc_cross(pf_ctx *ctx, int mode, const pf_plc_segment *seg, const pf_peak_region *box,
+                 size_t ncand, const void *groups, const pf_plc_group_layout *gl,
+                 const void *f_lo, size_t f_lo_stride, int min_mass,
+                 size_t capacity, void *plcgroups, const pf_plc_out_layout *ol,
+                 unsigned int *cand_of, int *rep_of, double *nz,
+                 size_t *count, size_t *unconverged);
+int pf_debug_plc_times(double *ms2);
 /* Per-particle payload of one block of the "timeless snapshot" (write_timeless_snapshot, src/write_snapshot.c:207-342)
    for this rank's slab, from the SoA columns in HBM: name = "ID  " (1 + global index as MYIDTYPE of id_bytes = 4 or 8,
    :648-664), "FMAX" float, "RMAX" int, "ZEL " / "2LPT" / "31PT" / "32PT" float[3] per particle (:700-855), and the last

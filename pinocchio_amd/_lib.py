@@ -62,6 +62,43 @@ class GroupLayout(C.Structure):
                 ("off_Vel_3LPT_2_prev", C.c_long)]
 
 
+PLC_LAST_CHECK = 0
+PLC_EVENTS = 1
+_dptr = C.POINTER(C.c_double)
+
+
+class PlcCosmology(C.Structure):
+    _fields_ = [("n", C.c_int), ("x", _dptr), ("comvdist", _dptr), ("hubble", _dptr), ("nk", C.c_int), ("grow", _dptr * 4), ("fomega", _dptr * 4),
+                ("logkmin", C.c_double), ("deltalogk", C.c_double), ("k_for_GM", C.c_double), ("rad_gm0", C.c_double), ("nsmooth", C.c_int),
+                ("k_gm_displ", _dptr)]
+
+
+class PlcReplication(C.Structure):
+    _fields_ = [("i", C.c_int), ("j", C.c_int), ("k", C.c_int), ("F1", C.c_double), ("F2", C.c_double)]
+
+
+class PlcGeometry(C.Structure):
+    _fields_ = [("center", C.c_double * 3), ("xvers", C.c_double * 3), ("yvers", C.c_double * 3), ("zvers", C.c_double * 3), ("aperture", C.c_double),
+                ("Fstop", C.c_double), ("InterPartDist", C.c_double), ("GSglobal", C.c_longlong * 3), ("nrep", C.c_size_t),
+                ("repls", C.POINTER(PlcReplication)), ("LastzForPLC", C.c_double), ("delta_z", C.c_double), ("nzbins", C.c_int)]
+
+
+class PlcSegment(C.Structure):
+    _fields_ = [("myseg", C.c_int), ("use_v31", C.c_int), ("z_seg", C.c_double), ("z_prev", C.c_double)]
+
+
+PLC_GROUP_FIELDS = ["off_Mass", "off_Pos", "off_name", "off_Flast", "off_good", "off_point", "off_Vel", "off_Vel_2LPT", "off_Vel_3LPT_1", "off_Vel_3LPT_2",
+                    "off_Vel_prev", "off_Vel_2LPT_prev", "off_Vel_3LPT_1_prev", "off_Vel_3LPT_2_prev"]
+
+
+class PlcGroupLayout(C.Structure):
+    _fields_ = [("stride", C.c_size_t)] + [(f, C.c_long) for f in PLC_GROUP_FIELDS]
+
+
+class PlcOutLayout(C.Structure):
+    _fields_ = [("stride", C.c_size_t), ("off_Mass", C.c_long), ("off_name", C.c_long), ("off_z", C.c_long), ("off_x", C.c_long), ("off_v", C.c_long)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -167,6 +204,12 @@ PROTOTYPES = {
                                                C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_double),
                                                C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "pf_debug_groupvel_times": (C.c_int, [C.POINTER(C.c_double)]),
+    "pf_plc_set_cosmology": (C.c_int, [_vp, C.POINTER(PlcCosmology)]),
+    "pf_plc_set_geometry": (C.c_int, [_vp, C.POINTER(PlcGeometry)]),
+    "pf_plc_cross": (C.c_int, [_vp, C.c_int, C.POINTER(PlcSegment), C.POINTER(PeakRegion), C.c_size_t, _vp, C.POINTER(PlcGroupLayout), _vp, C.c_size_t, C.c_int,
+                               C.c_size_t, _vp, C.POINTER(PlcOutLayout), C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_size_t),
+                               C.POINTER(C.c_size_t)]),
+    "pf_debug_plc_times": (C.c_int, [C.POINTER(C.c_double)]),
     "pf_set_collapse_model": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "pf_set_modified_gravity": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "pf_set_tabulated_ct": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),

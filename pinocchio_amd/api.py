@@ -50,6 +50,16 @@ def _region(region):
     return _lib.PeakRegion((C.c_int * 3)(*map(int, start)), (C.c_int * 3)(*map(int, length)), (C.c_int * 3)(*map(int, safe)))
 
 
+PLC_LAST_CHECK, PLC_EVENTS = _lib.PLC_LAST_CHECK, _lib.PLC_EVENTS
+
+
+def plc_times():
+    """device ms of the last plc_cross: (candidate passes, root + store passes); zeros without PF_PLC_TIMES=1 (pf_debug_plc_times)"""
+    ms = (C.c_double * 2)()
+    _lib.load().pf_debug_plc_times(ms)
+    return float(ms[0]), float(ms[1])
+
+
 def debug_peaks(fmax: np.ndarray, flast: float, region=None):
     """count_peaks (src/fragment.c:605-706) by the device kernel on a caller's [n][n][n] fp32 field -> (npeaks, ngood)"""
     L = _lib.load()
@@ -244,6 +254,34 @@ def group_layout(stride, off_Mass=-1, off_Vel=-1, off_Vel_2LPT=-1, off_Vel_3LPT_
     """byte offsets of Mass and the Vel* / Vel*_prev fields of a group record (pf_group_layout); negative = absent"""
     return _lib.GroupLayout(int(stride), int(off_Mass), int(off_Vel), int(off_Vel_2LPT), int(off_Vel_3LPT_1), int(off_Vel_3LPT_2), int(off_Vel_prev),
                             int(off_Vel_2LPT_prev), int(off_Vel_3LPT_1_prev), int(off_Vel_3LPT_2_prev))
+
+
+def plc_group_layout(stride, off_Mass, off_Pos, off_Flast, off_name=-1, off_good=-1, off_point=-1, off_Vel=-1, off_Vel_2LPT=-1, off_Vel_3LPT_1=-1,
+                     off_Vel_3LPT_2=-1, off_Vel_prev=-1, off_Vel_2LPT_prev=-1, off_Vel_3LPT_1_prev=-1, off_Vel_3LPT_2_prev=-1):
+    """byte offsets of the fields of a group record the light-cone test reads (pf_plc_group_layout); negative = absent"""
+    return _lib.PlcGroupLayout(int(stride), int(off_Mass), int(off_Pos), int(off_name), int(off_Flast), int(off_good), int(off_point), int(off_Vel),
+                               int(off_Vel_2LPT), int(off_Vel_3LPT_1), int(off_Vel_3LPT_2), int(off_Vel_prev), int(off_Vel_2LPT_prev),
+                               int(off_Vel_3LPT_1_prev), int(off_Vel_3LPT_2_prev))
+
+
+def plc_out_dtype(double_products=False):
+    """plcgroup_data (src/pinocchio.h:430-435) as the compiler lays it out: 48 bytes, 72 with PRODFLOAT double"""
+    f, pb = ("<f8", 8) if double_products else ("<f4", 4)
+    return np.dtype({"names": ["Mass", "name", "z", "x", "v"], "formats": ["<i4", "<u8", f, (f, 3), (f, 3)],
+                     "offsets": [0, 8, 16, 16 + pb, 16 + 4 * pb], "itemsize": 72 if double_products else 48})
+
+
+def plc_out_layout(dtype):
+    """pf_plc_out_layout of a structured dtype with (some of) the fields Mass, name, z, x, v"""
+    off = {k: (dtype.fields[k][1] if k in dtype.fields else -1) for k in ("Mass", "name", "z", "x", "v")}
+    return _lib.PlcOutLayout(dtype.itemsize, off["Mass"], off["name"], off["z"], off["x"], off["v"])
+
+
+def plc_group_layout_of(dtype):
+    """pf_plc_group_layout of a structured dtype whose fields carry the reference's names (Mass, Pos, Flast, name, good, point, Vel, ...)"""
+    kw = {"off_" + k: dtype.fields[k][1] for k in ("Mass", "Pos", "Flast", "name", "good", "point", "Vel", "Vel_2LPT", "Vel_3LPT_1", "Vel_3LPT_2",
+                                                   "Vel_prev", "Vel_2LPT_prev", "Vel_3LPT_1_prev", "Vel_3LPT_2_prev") if k in dtype.fields}
+    return plc_group_layout(dtype.itemsize, **kw)
 
 
 def _group_ids(group_id, count):
@@ -884,6 +922,83 @@ class Fmax:
                                             int(ngroups), C.byref(group_layout) if group_layout is not None else None, C.byref(loose), C.byref(grouped),
                                             C.byref(mism)))
         return int(loose.value), int(grouped.value), int(mism.value)
+
+    def plc_set_cosmology(self, x, comvdist, hubble, grow, fomega, k_for_GM=0.0, logkmin=-3.0, deltalogk=0.5, rad_gm0=0.0, k_gm_displ=None):
+        """the splines the light-cone test reads (pf_plc_set_cosmology), all at the knots x = -log10(1 + z): comvdist, hubble [n];
+        grow, fomega [4][nk][n] (orders 1, 2, 31, 32; grow as log10).  nk = 1 reads k_for_GM; nk > 1 reads the k-bins logkmin +
+        j deltalogk, Rad_GM[0] and k_GM_displ."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        cd = np.ascontiguousarray(comvdist, dtype=np.float64)
+        hb = np.ascontiguousarray(hubble, dtype=np.float64)
+        gr = np.ascontiguousarray(grow, dtype=np.float64)
+        fo = np.ascontiguousarray(fomega, dtype=np.float64)
+        n = x.size
+        if gr.ndim == 2:
+            gr, fo = gr[:, None, :], fo[:, None, :]
+        if cd.shape != (n,) or hb.shape != (n,) or gr.ndim != 3 or gr.shape[0] != 4 or gr.shape[2] != n or fo.shape != gr.shape:
+            raise ValueError(f"tables of shapes {cd.shape}, {hb.shape}, {gr.shape}, {fo.shape} for {n} knots")
+        gr, fo = np.ascontiguousarray(gr), np.ascontiguousarray(fo)
+        kg = np.ascontiguousarray(k_gm_displ, dtype=np.float64) if k_gm_displ is not None else None
+        cs = _lib.PlcCosmology(n=n, x=_dp(x), comvdist=_dp(cd), hubble=_dp(hb), nk=gr.shape[1], grow=(_lib._dptr * 4)(*[_dp(gr[f]) for f in range(4)]),
+                               fomega=(_lib._dptr * 4)(*[_dp(fo[f]) for f in range(4)]), logkmin=logkmin, deltalogk=deltalogk, k_for_GM=k_for_GM,
+                               rad_gm0=rad_gm0, nsmooth=kg.size if kg is not None else 0, k_gm_displ=_dp(kg) if kg is not None else None)
+        self._chk(self.L.pf_plc_set_cosmology(self.h, C.byref(cs)))
+
+    def plc_set_geometry(self, center, xvers, yvers, zvers, aperture, Fstop, InterPartDist, GSglobal, repls, LastzForPLC=0.0, delta_z=1.0, nzbins=0):
+        """the cone and its replications (pf_plc_set_geometry); repls: rows (i, j, k, F1, F2) (src/pinocchio.h:412-416)"""
+        rp = [tuple(r) for r in repls]
+        arr = (_lib.PlcReplication * max(len(rp), 1))(*[_lib.PlcReplication(int(r[0]), int(r[1]), int(r[2]), float(r[3]), float(r[4])) for r in rp])
+        v3 = lambda a: (C.c_double * 3)(*map(float, a))
+        gm = _lib.PlcGeometry(center=v3(center), xvers=v3(xvers), yvers=v3(yvers), zvers=v3(zvers), aperture=aperture, Fstop=Fstop, InterPartDist=InterPartDist,
+                              GSglobal=(C.c_longlong * 3)(*map(int, GSglobal)), nrep=len(rp), repls=arr, LastzForPLC=LastzForPLC, delta_z=delta_z, nzbins=nzbins)
+        self._plc_nzbins = int(nzbins)
+        self._chk(self.L.pf_plc_set_geometry(self.h, C.byref(gm)))
+
+    def plc_cross(self, mode, myseg, z_seg, stabl, groups, group_layout=None, z_prev=0.0, use_v31=False, f_lo=None, min_mass=0, capacity=None, out_dtype=None,
+                  nz=None):
+        """the light-cone test of build_groups() on `groups` (pf_plc_cross): a structured array of group states (group_layout None:
+        the layout of its dtype, plc_group_layout_of) -> (records, cand_of, rep_of, count, unconverged); records: a structured array
+        of out_dtype (None: plc_out_dtype) with the first min(count, capacity) crossings in (candidate, replication) order.  mode
+        PLC_EVENTS reads the lower end of every candidate's interval from f_lo.  nz: the n(z) histogram, added to in place."""
+        pt = np.float64 if self.double_products else np.float32
+        if not groups.flags.c_contiguous:
+            raise ValueError("groups must be contiguous")
+        gl = group_layout if group_layout is not None else plc_group_layout_of(groups.dtype)
+        ncand = groups.nbytes // gl.stride if gl.stride else 0
+        od = np.dtype(out_dtype) if out_dtype is not None else plc_out_dtype(self.double_products)
+        ol = plc_out_layout(od)
+        fl = np.ascontiguousarray(f_lo, dtype=pt) if f_lo is not None else None
+        if fl is not None and fl.size != ncand:
+            raise ValueError(f"{fl.size} lower ends for {ncand} candidates")
+        if nz is not None and not (nz.dtype == np.float64 and nz.flags.c_contiguous and nz.size == getattr(self, "_plc_nzbins", -1)):
+            raise ValueError("nz must be a contiguous float64 array of nzbins values")
+        seg = _lib.PlcSegment(int(myseg), int(bool(use_v31)), float(z_seg), float(z_prev))
+        rg = _region((stabl, (1, 1, 1), (0, 0, 0)))
+        # a first call counts; a second one fetches when the capacity was left to the count
+        cap = ncand if capacity is None else int(capacity)
+        rec = np.zeros(cap, dtype=od)
+        cand = np.empty(cap, dtype=np.uint32)
+        rep = np.empty(cap, dtype=np.int32)
+        cnt, unc = C.c_size_t(), C.c_size_t()
+
+        def call(cap_):
+            self._chk(self.L.pf_plc_cross(self.h, int(mode), C.byref(seg), C.byref(rg), ncand, groups.ctypes.data_as(C.c_void_p) if ncand else None, C.byref(gl),
+                                          fl.ctypes.data_as(C.c_void_p) if fl is not None else None, fl.itemsize if fl is not None else 0, int(min_mass), cap_,
+                                          rec.ctypes.data_as(C.c_void_p), C.byref(ol), cand.ctypes.data_as(C.POINTER(C.c_uint)),
+                                          rep.ctypes.data_as(C.POINTER(C.c_int)), _dp(nz) if nz is not None else None, C.byref(cnt), C.byref(unc)))
+        if capacity is None:
+            keep = nz.copy() if nz is not None else None
+            call(cap)
+            if cnt.value > cap:   # more crossings than candidates: once more with room for all of them
+                cap = int(cnt.value)
+                rec, cand, rep = np.zeros(cap, dtype=od), np.empty(cap, dtype=np.uint32), np.empty(cap, dtype=np.int32)
+                if nz is not None:
+                    nz[:] = keep
+                call(cap)
+        else:
+            call(cap)
+        m = min(int(cnt.value), cap)
+        return rec[:m], cand[:m], rep[:m], int(cnt.value), int(unc.value)
 
     def organize(self, records: np.ndarray, frag_pos: np.ndarray, layout=None):
         """sort_and_organize() (src/fragment.c:484-520) on records the caller holds (contributions of several ranks to one

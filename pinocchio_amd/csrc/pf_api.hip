@@ -205,6 +205,7 @@ struct pf_ctx {
   bool transposed; // spectra cross the boundary as [ky_local][kx][kz] (pf_set_transposed_spectra)
   int ct_flavour; // table interpolation of the build: 0 BILINEAR_SPLINE, 1 TRILINEAR, 2 ALL_SPLINE (pf_set_ct_interpolation)
   int lpt_order;  // 3: -DTWO_LPT -DTHREE_LPT (default), 2: -DTWO_LPT only, 1: Zel'dovich only (pf_set_lpt_order)
+  void *plc = nullptr;  // what pf_plc_set_cosmology / pf_plc_set_geometry keep (pf_plc.hip owns it: pf_plc_release)
   double *partials_src;  // PF_NBLK
   // general path: grid sizes that are not a power of two (one rank, fp64) go through library transforms
   bool general;
@@ -564,6 +565,7 @@ extern "C" int pf_destroy(pf_ctx *c) {
   pf_rccl_release(c->rccl); c->rccl = nullptr;
   delete c->loopback; c->loopback = nullptr;
   handoff_release(c);
+  pf_plc_release(c->plc); c->plc = nullptr;
   hipFree(c->dk); hipFree(c->blockA); hipFree(c->recvA); hipFree(c->tw); hipFree(c->blockA2); hipFree(c->recvA2); hipFree(c->dk_full); hipFree(c->inv_own[0]); hipFree(c->inv_own[1]);
   for (int i = 0; i < 6; i++) hipFree(c->B[i]);
   hipFree(c->blockS); hipFree(c->blockB2);
@@ -2033,6 +2035,7 @@ extern "C" int pf_drop_prev(pf_ctx *c) {
   return 0;
 }
 extern "C" int pf_prev_shifts(pf_ctx *c) { return c ? c->prev_shifts : -1; }
+void **pf_ctx_plc_slot(pf_ctx *c) { return &c->plc; }
 void pf_ctx_prev_view(pf_ctx *c, const void **prev, int *shifts, int *lpt_order) { *prev = c->vel12_prev; *shifts = c->prev_shifts; *lpt_order = c->lpt_order; }
 
 // The two columns into records the caller holds -- products[i].zacc / .group_ID of a -DSNAPSHOT build --, the merge of

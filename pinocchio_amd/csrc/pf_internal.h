@@ -361,6 +361,9 @@ size_t pf_refresh_first_bad(const unsigned int *a, size_t upto, unsigned long lo
 int pf_refresh_fields(const char *who, int rank, int pb, int shifts, const pf_product_layout *l, const pf_prev_layout *p, PfRefreshFields *f);
 int pf_refresh_to_records(pf_ctx *c, const PfCtxView &v, const char *who, const PfRefreshScratch &s, size_t m, size_t count, void *frag, size_t stride,
                           const PfRefreshFields &f);
+// ---- pf_plc.hip: the past-light-cone test of build_groups(); the context keeps one pointer for it and frees it in pf_destroy ----
+void **pf_ctx_plc_slot(pf_ctx *c);
+void pf_plc_release(void *state);
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);
