@@ -694,6 +694,60 @@ int pf_plc_cross(pf_ctx *ctx, int mode, const pf_plc_segment *seg, const pf_peak
                  unsigned int *cand_of, int *rep_of, double *nz,
                  size_t *count, size_t *unconverged);
 int pf_debug_plc_times(double *ms2);
+/* --- the halo catalogue and the mass function of an output on the device (src/build_groups.c:899-905) ---
+   At every output redshift build_groups() runs write_catalog() (src/write_halos.c:227-318) and compute_mf() (:35-65): one loop
+   over groups[] that, for every group with point >= 0 && good && Mass >= MinHaloMass, evaluates set_obj, set_weight, set_obj_vel,
+   q2x and vel (src/build_groups.c:1354-1460, :1554-1643) at F = outputs.F[iout] and fills a catalog_data record
+   (src/pinocchio.h:515-524), and a second one that bins the same groups by log10(Mass * ParticleMass).  pf_catalog is both loops
+   (write_halos.c:268-318 and :46-65) for a host that keeps groups[]; the file, its headers, the MPI_Reduce of the histogram, the
+   analytic mass function and write_histories stay with the host (INTEGRATION.md has the call site).
+   It reads the splines of pf_plc_set_cosmology -- which must have been called; pf_plc_set_geometry need not -- and works on a
+   context that has run no sweep.
+   groups: `ngroups` records of `gl->stride` bytes, the first one the reference's loop visits (groups + FILAMENT + 1), read through
+   the layout of pf_plc_cross: Mass (int), Pos (PRODFLOAT[3]), name, good, point and the eight velocities; a negative offset =
+   absent (velocities read zero, an absent good or point passes, an absent name reads zero; Mass and Pos must be there; Flast is
+   not read and need not be named).  The host threads pack what goes up: 27 PRODFLOATs, Mass and one byte -- 113 bytes per group
+   (221 with PF_FLAG_DOUBLE_PRODUCTS); name stays on the host.  What comes down is 10 PRODFLOATs and the batch index per record.
+   seg: as in pf_plc_cross (myseg, z_seg, z_prev for set_weight; use_v31 = 0 reproduces build_groups.c:1588 as written).
+   box->start is subbox.stabl and box->len is subbox.Lgwbl (safe is not read).
+   par: F = outputs.F[iout] (rounded to PRODFLOAT as set_obj's argument is; z = F - 1), InterPartDist, ParticleMass, hfactor
+   (params.Hubble100 with OutputInH100, else 1: write_halos.c:262-265), GSglobal, pbc = subbox.pbc, min_mass = MinHaloMass.
+   Record of a passing group (write_halos.c:289-315), every expression rounded where the reference's C rounds it:
+     name = the group's, n = Mass, M = Mass * ParticleMass * hfactor
+     q[j] = Pos[j] + stabl[j]; if (q < 0) q += GSglobal[j]; if (q >= GSglobal[j]) q -= GSglobal[j]; q *= InterPartDist * hfactor
+     x[j] = q2x at order ORDER_FOR_CATALOG = 3 (capped by pf_set_lpt_order), wrapped into [0, len[j]) where pbc[j] is set
+            (:1595-1600: >= Box first, then < 0), + stabl[j], then the same two wraps and the same factor as q
+     v[j] = vel(j) with set_obj_vel's factors at z (Hubble(z) from the table of pf_plc_set_cosmology)
+   Records come in ascending batch index, the same from run to run: a flag pass, a scan, a record pass; no atomic decides an order.
+   *count is the number of passing groups; the first min(*count, capacity) are written into the fields `ol` names of record j of
+   `catalog` (name 8 bytes, M, x[3], v[3], q[3] PRODFLOATs, n an int; negative = absent).  Bytes of a record that the layout does
+   not name -- pad, n under LIGHT_OUTPUT -- and records beyond those written are left as the caller had them.  group_of (optional)
+   gets the batch index of every written record.
+   bins (NULL: no mass function): ninbin and massinbin, nbin entries each, are SET to the mf.ninbin_local / mf.massinbin_local of
+   these groups -- all passing groups, whatever the capacity; the MPI_Reduce stays the caller's.  The bin of a group is
+   (int)((log10(Mass * ParticleMass) - mmin) / deltam), skipped outside [0, nbin) (write_halos.c:59-62), with mmin as
+   src/initialization.c:1122 forms it and deltam = DELTAM.  The device evaluates no log10: the call turns the bins into nbin + 1
+   integer thresholds -- the smallest Mass >= 1 of every bin, by bisection over Mass with the host libm's log10 -- and the device
+   bins by binary search, which is the reference's binning to the last bit wherever log10(Mass * ParticleMass) does not decrease
+   with Mass.  A group with Mass < 1 is never binned.  The sums are integers on the device (a count and a 64-bit sum of Mass per
+   bin); massinbin[b] = (double)sumMass[b] * ParticleMass, within (n_b + 1) 2^-53 relative of the reference's running sum of
+   doubles and independent of the order of groups[].
+   Refused (return 1, pf_last_error, *count = 0): null arguments, no cosmology set, myseg < 0, F not finite or <= 0, InterPartDist
+   or hfactor <= 0, ParticleMass or deltam <= 0 with bins, nbin outside 0..2^20, len or GSglobal <= 0, a layout field that leaves
+   its record, more than 2^31 - 1 groups.
+   pf_debug_catalog_times: with PF_CATALOG_TIMES=1 in the environment pf_catalog measures its device part between two events; ms2 =
+   the device ms of the last call's flag + scan passes and of its record + histogram passes.  Zeros otherwise.
+   pf_debug_catalog_parts: the host's wall ms of the last call's four parts -- pack, upload, device (allocations and waits
+   included), download + records -- for profiles/tools/catalog_time.py. */
+typedef struct { double F, InterPartDist, ParticleMass, hfactor; long long GSglobal[3]; int pbc[3]; int min_mass; } pf_catalog_params;
+typedef struct { size_t stride; long off_name, off_M, off_x, off_v, off_q, off_n; } pf_catalog_out_layout;   /* bytes, negative = absent */
+typedef struct { int nbin; double mmin, deltam; } pf_mf_bins;
+int pf_catalog(pf_ctx *ctx, const pf_plc_segment *seg, const pf_peak_region *box, const pf_catalog_params *par,
+               size_t ngroups, const void *groups, const pf_plc_group_layout *gl,
+               size_t capacity, void *catalog, const pf_catalog_out_layout *ol, unsigned int *group_of,
+               const pf_mf_bins *bins, int *ninbin, double *massinbin, size_t *count);
+int pf_debug_catalog_times(double *ms2);
+int pf_debug_catalog_parts(double *ms4);
 /* Per-particle payload of one block of the "timeless snapshot" (write_timeless_snapshot, src/write_snapshot.c:207-342)
    for this rank's slab, from the SoA columns in HBM: name = "ID  " (1 + global index as MYIDTYPE of id_bytes = 4 or 8,
    :648-664), "FMAX" float, "RMAX" int, "ZEL " / "2LPT" / "31PT" / "32PT" float[3] per particle (:700-855), and the last

@@ -99,6 +99,20 @@ class PlcOutLayout(C.Structure):
     _fields_ = [("stride", C.c_size_t), ("off_Mass", C.c_long), ("off_name", C.c_long), ("off_z", C.c_long), ("off_x", C.c_long), ("off_v", C.c_long)]
 
 
+class CatalogParams(C.Structure):
+    _fields_ = [("F", C.c_double), ("InterPartDist", C.c_double), ("ParticleMass", C.c_double), ("hfactor", C.c_double), ("GSglobal", C.c_longlong * 3),
+                ("pbc", C.c_int * 3), ("min_mass", C.c_int)]
+
+
+class CatalogOutLayout(C.Structure):
+    _fields_ = [("stride", C.c_size_t), ("off_name", C.c_long), ("off_M", C.c_long), ("off_x", C.c_long), ("off_v", C.c_long), ("off_q", C.c_long),
+                ("off_n", C.c_long)]
+
+
+class MfBins(C.Structure):
+    _fields_ = [("nbin", C.c_int), ("mmin", C.c_double), ("deltam", C.c_double)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -210,6 +224,10 @@ PROTOTYPES = {
                                C.c_size_t, _vp, C.POINTER(PlcOutLayout), C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_size_t),
                                C.POINTER(C.c_size_t)]),
     "pf_debug_plc_times": (C.c_int, [C.POINTER(C.c_double)]),
+    "pf_catalog": (C.c_int, [_vp, C.POINTER(PlcSegment), C.POINTER(PeakRegion), C.POINTER(CatalogParams), C.c_size_t, _vp, C.POINTER(PlcGroupLayout), C.c_size_t, _vp,
+                             C.POINTER(CatalogOutLayout), C.POINTER(C.c_uint), C.POINTER(MfBins), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_size_t)]),
+    "pf_debug_catalog_times": (C.c_int, [C.POINTER(C.c_double)]),
+    "pf_debug_catalog_parts": (C.c_int, [C.POINTER(C.c_double)]),
     "pf_set_collapse_model": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "pf_set_modified_gravity": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "pf_set_tabulated_ct": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),

@@ -60,6 +60,21 @@ def plc_times():
     return float(ms[0]), float(ms[1])
 
 
+def catalog_times():
+    """device ms of the last catalog: (flag + scan passes, record + histogram passes); zeros without PF_CATALOG_TIMES=1
+    (pf_debug_catalog_times)"""
+    ms = (C.c_double * 2)()
+    _lib.load().pf_debug_catalog_times(ms)
+    return float(ms[0]), float(ms[1])
+
+
+def catalog_parts():
+    """the host's wall ms of the last catalog: (pack, upload, device, download + records) (pf_debug_catalog_parts)"""
+    ms = (C.c_double * 4)()
+    _lib.load().pf_debug_catalog_parts(ms)
+    return tuple(float(x) for x in ms)
+
+
 def debug_peaks(fmax: np.ndarray, flast: float, region=None):
     """count_peaks (src/fragment.c:605-706) by the device kernel on a caller's [n][n][n] fp32 field -> (npeaks, ngood)"""
     L = _lib.load()
@@ -275,6 +290,24 @@ def plc_out_layout(dtype):
     """pf_plc_out_layout of a structured dtype with (some of) the fields Mass, name, z, x, v"""
     off = {k: (dtype.fields[k][1] if k in dtype.fields else -1) for k in ("Mass", "name", "z", "x", "v")}
     return _lib.PlcOutLayout(dtype.itemsize, off["Mass"], off["name"], off["z"], off["x"], off["v"])
+
+
+def catalog_dtype(double_products=False, light=False):
+    """catalog_data (src/pinocchio.h:515-524) as the compiler lays it out: 56 bytes, 96 with PRODFLOAT double; 48 / 88 with
+    LIGHT_OUTPUT (no n, no pad)"""
+    f, pb = ("<f8", 8) if double_products else ("<f4", 4)
+    names, formats, offsets = ["name", "M", "x", "v", "q"], ["<u8", f, (f, 3), (f, 3), (f, 3)], [0, 8, 8 + pb, 8 + 4 * pb, 8 + 7 * pb]
+    size = 8 + 10 * pb
+    if not light:
+        names, formats, offsets = names + ["n", "pad"], formats + ["<i4", "<i4"], offsets + [size, size + 4]
+        size += 8
+    return np.dtype({"names": names, "formats": formats, "offsets": offsets, "itemsize": size})
+
+
+def catalog_out_layout(dtype):
+    """pf_catalog_out_layout of a structured dtype with (some of) the fields name, M, x, v, q, n"""
+    off = {k: (dtype.fields[k][1] if k in dtype.fields else -1) for k in ("name", "M", "x", "v", "q", "n")}
+    return _lib.CatalogOutLayout(dtype.itemsize, off["name"], off["M"], off["x"], off["v"], off["q"], off["n"])
 
 
 def plc_group_layout_of(dtype):
@@ -999,6 +1032,45 @@ class Fmax:
             call(cap)
         m = min(int(cnt.value), cap)
         return rec[:m], cand[:m], rep[:m], int(cnt.value), int(unc.value)
+
+    def catalog(self, F, myseg, z_seg, stabl, Lgwbl, groups, InterPartDist, ParticleMass, GSglobal, hfactor=1.0, pbc=(0, 0, 0), min_mass=0, group_layout=None,
+                z_prev=0.0, use_v31=False, capacity=None, out_dtype=None, out=None, bins=None):
+        """write_catalog() and compute_mf() of one output on `groups` (pf_catalog): a structured array of group states (group_layout
+        None: the layout of its dtype, plc_group_layout_of; Flast need not be there) -> (records, group_of, count, ninbin, massinbin).
+        records: a structured array of out_dtype (None: catalog_dtype) with the first min(count, capacity) passing groups in batch
+        order -- written into `out` where one is given (its other bytes stay) --, group_of their batch indices.  bins = (nbin, mmin,
+        deltam): the local mass function of all passing groups; None: ninbin and massinbin are None."""
+        if not groups.flags.c_contiguous:
+            raise ValueError("groups must be contiguous")
+        if group_layout is not None:
+            gl = group_layout
+        else:
+            names = groups.dtype.fields
+            gl = plc_group_layout_of(groups.dtype) if "Flast" in names else plc_group_layout(groups.dtype.itemsize, off_Flast=-1, **{
+                "off_" + k: names[k][1] for k in ("Mass", "Pos", "name", "good", "point", "Vel", "Vel_2LPT", "Vel_3LPT_1", "Vel_3LPT_2", "Vel_prev", "Vel_2LPT_prev",
+                                                  "Vel_3LPT_1_prev", "Vel_3LPT_2_prev") if k in names})
+        ngroups = groups.nbytes // gl.stride if gl.stride else 0
+        od = np.dtype(out_dtype) if out_dtype is not None else (out.dtype if out is not None else catalog_dtype(self.double_products))
+        ol = catalog_out_layout(od)
+        cap = (ngroups if out is None else len(out)) if capacity is None else int(capacity)
+        rec = out if out is not None else np.zeros(cap, dtype=od)
+        if not (rec.flags.c_contiguous and rec.dtype.itemsize == od.itemsize and len(rec) >= cap):
+            raise ValueError("out must be a contiguous array of at least `capacity` records of out_dtype")
+        gof = np.empty(cap, dtype=np.uint32)
+        seg = _lib.PlcSegment(int(myseg), int(bool(use_v31)), float(z_seg), float(z_prev))
+        rg = _region((stabl, Lgwbl, (0, 0, 0)))
+        par = _lib.CatalogParams(F=float(F), InterPartDist=float(InterPartDist), ParticleMass=float(ParticleMass), hfactor=float(hfactor),
+                                 GSglobal=(C.c_longlong * 3)(*map(int, GSglobal)), pbc=(C.c_int * 3)(*map(int, pbc)), min_mass=int(min_mass))
+        mb = nin = mas = None
+        if bins is not None:
+            mb = _lib.MfBins(int(bins[0]), float(bins[1]), float(bins[2]))
+            nin, mas = np.zeros(max(mb.nbin, 0), dtype=np.int32), np.zeros(max(mb.nbin, 0), dtype=np.float64)
+        cnt = C.c_size_t()
+        self._chk(self.L.pf_catalog(self.h, C.byref(seg), C.byref(rg), C.byref(par), ngroups, groups.ctypes.data_as(C.c_void_p) if ngroups else None, C.byref(gl), cap,
+                                    rec.ctypes.data_as(C.c_void_p), C.byref(ol), gof.ctypes.data_as(C.POINTER(C.c_uint)), C.byref(mb) if mb is not None else None,
+                                    nin.ctypes.data_as(C.POINTER(C.c_int)) if nin is not None else None, _dp(mas) if mas is not None else None, C.byref(cnt)))
+        m = min(int(cnt.value), cap)
+        return rec[:m], gof[:m], int(cnt.value), nin, mas
 
     def organize(self, records: np.ndarray, frag_pos: np.ndarray, layout=None):
         """sort_and_organize() (src/fragment.c:484-520) on records the caller holds (contributions of several ranks to one

@@ -364,6 +364,9 @@ int pf_refresh_to_records(pf_ctx *c, const PfCtxView &v, const char *who, const 
 // ---- pf_plc.hip: the past-light-cone test of build_groups(); the context keeps one pointer for it and frees it in pf_destroy ----
 void **pf_ctx_plc_slot(pf_ctx *c);
 void pf_plc_release(void *state);
+// ---- pf_catalog.hip: the halo catalogue and the mass function of an output; it reads the tables the light-cone state keeps ----
+struct PfPlcTab;
+bool pf_plc_tables(pf_ctx *c, PfPlcTab *tab, int *tab_doubles);   // false: no cosmology set
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);

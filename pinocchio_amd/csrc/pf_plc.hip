@@ -199,6 +199,14 @@ static PfPlcState *plc_state(pf_ctx *c) {
   return (PfPlcState *)*slot;
 }
 
+// what pf_catalog.hip reads of the state: the tables as pf_plc_set_cosmology left them on the device; false while there are none
+bool pf_plc_tables(pf_ctx *c, PfPlcTab *tab, int *tab_doubles) {
+  const PfPlcState *s = (const PfPlcState *)*pf_ctx_plc_slot(c);
+  if (!s || !s->have_cosmo) return false;
+  *tab = s->tab; *tab_doubles = s->tab_doubles;
+  return true;
+}
+
 extern "C" int pf_plc_set_cosmology(pf_ctx *c, const pf_plc_cosmology *cs) {
   const char *who = "pf_plc_set_cosmology";
   if (!c || !cs) return pf_fail(0, "%s: null argument", who);

@@ -217,6 +217,30 @@ template <class T> PF_PLC_HD bool pf_plc_root(const PfPlcTab &t, const PfPlcGeom
   return false;
 }
 
+// set_obj_vel (:1446-1460) at z = F - 1 with Hubble(z) from its table, and vel (:1607-1643) of the three axes: what store_PLC and the
+// catalogue (pf_catalog_core.h) write as a group's velocity
+template <class T> PF_PLC_HD void pf_plc_vel3(const PfPlcTab &t, double ipd, const PfPlcSegIn &sg, const PfPlcK &k, const PfPlcObj<T> &o, const PfPlcW<T> &w, T F, T vel[3]) {
+  const double z = F - 1.0;
+  const PfPlcX p = pf_plc_locate(t, z);
+  const T fac = (T)(pf_plc_spline(t, 1, p) / (1. + z) * ipd);
+  T Dv[4];
+  for (int f = 0; f < 4; f++) Dv[f] = (T)(fac * pf_plc_growth(t, 4 + f, k, p));
+  for (int i = 0; i < 3; i++) {
+    T vv;
+    if (!sg.myseg) {
+      vv = o.v[0][i] * Dv[0] * w.w[0];
+      if (sg.order > 1) vv += o.v[1][i] * Dv[1] * w.w[1];
+      if (sg.order > 2) vv += o.v[2][i] * Dv[2] * w.w[2] + o.v[3][i] * Dv[3] * w.w[3];
+    } else {
+      vv = (T)((o.v[4][i] * (1. - w.w[0]) + o.v[0][i] * w.w[0]) * Dv[0]);
+      if (sg.order > 1) vv = (T)(vv + (o.v[5][i] * (1. - w.w[1]) + o.v[1][i] * w.w[1]) * Dv[1]);
+      if (sg.order > 2)
+        vv = (T)(vv + ((o.v[6][i] * (1. - w.w[2]) + o.v[2][i] * w.w[2]) * Dv[2] + (o.v[7][i] * (1. - w.w[3]) + o.v[3][i] * w.w[3]) * Dv[3]));
+    }
+    vel[i] = vv;
+  }
+}
+
 // store_PLC (:1764-1822) at F: false when the group lies outside the aperture.  rec = z, x[3], v[3]; *iz the bin of the n(z)
 // histogram, -1 where the reference would write outside nz[]
 template <class T> PF_PLC_HD bool pf_plc_store(const PfPlcTab &t, const PfPlcGeom &g, const PfPlcSegIn &sg, const PfPlcK &k, const PfPlcSeg &s,
@@ -230,27 +254,12 @@ template <class T> PF_PLC_HD bool pf_plc_store(const PfPlcTab &t, const PfPlcGeo
   double theta = 90.0;
   if (rho > 0) theta = -acos((x[0] * g.zvers[0] + x[1] * g.zvers[1] + x[2] * g.zvers[2]) / rho) * 180. / PF_PLC_PI + 90.;
   if (!(90. - theta < g.aperture)) return false;
-  // set_obj_vel (:1446-1460) with Hubble(z) from its table, and vel (:1607-1643)
-  const double z = F - 1.0;
-  const PfPlcX p = pf_plc_locate(t, z);
-  const T fac = (T)(pf_plc_spline(t, 1, p) / (1. + z) * g.ipd);
-  T Dv[4];
-  for (int f = 0; f < 4; f++) Dv[f] = (T)(fac * pf_plc_growth(t, 4 + f, k, p));
+  T vv[3];
+  pf_plc_vel3<T>(t, g.ipd, sg, k, o, w, F, vv);
   rec[0] = (T)(F - 1.0);
   for (int i = 0; i < 3; i++) {
-    T vv;
-    if (!sg.myseg) {
-      vv = o.v[0][i] * Dv[0] * w.w[0];
-      if (sg.order > 1) vv += o.v[1][i] * Dv[1] * w.w[1];
-      if (sg.order > 2) vv += o.v[2][i] * Dv[2] * w.w[2] + o.v[3][i] * Dv[3] * w.w[3];
-    } else {
-      vv = (T)((o.v[4][i] * (1. - w.w[0]) + o.v[0][i] * w.w[0]) * Dv[0]);
-      if (sg.order > 1) vv = (T)(vv + (o.v[5][i] * (1. - w.w[1]) + o.v[1][i] * w.w[1]) * Dv[1]);
-      if (sg.order > 2)
-        vv = (T)(vv + ((o.v[6][i] * (1. - w.w[2]) + o.v[2][i] * w.w[2]) * Dv[2] + (o.v[7][i] * (1. - w.w[3]) + o.v[3][i] * w.w[3]) * Dv[3]));
-    }
     rec[1 + i] = x[i];
-    rec[4 + i] = vv;
+    rec[4 + i] = vv[i];
   }
   int b = (int)((rec[0] - g.lastz) / g.delta_z);
   if (b == g.nzbins) b--;
