@@ -128,9 +128,9 @@ class Case:
     def L(self):
         """the largest coordinate magnitude of the case, in cells: positions in the sub-box, in the global box, and the box itself"""
         if not self.n:
-            return float(GS)
+            return float(self.gs[0])
         p = self.groups["Pos"].astype(np.float64)
-        return float(max(np.abs(p).max(), np.abs(p + np.asarray(self.stabl)).max(), GS) + 8.0)
+        return float(max(np.abs(p).max(), np.abs(p + np.asarray(self.stabl)).max(), self.gs[0]) + 8.0)
 
     def band(self):
         """8 ulp32(L) cells, plc_cases.Case.band: the sum of at most eight PRODFLOAT terms of magnitude <= L that a position is"""
@@ -162,10 +162,10 @@ class Case:
         assert rec["q"].tobytes() == np.ascontiguousarray(o["q"][sel]).tobytes(), self.name
         scale = self.ipd * self.hfactor
         if m:
-            top = T(np.float64(GS) * scale)
+            top = T(np.float64(self.gs[0]) * scale)
             x = rec["x"].astype(np.float64)
             assert (rec["x"] >= 0).all() and (rec["x"] <= top).all(), (self.name, float(x.min()), float(x.max()))
-            Lbox = GS * scale
+            Lbox = self.gs[0] * scale
             dx = np.abs(x - o["x"][sel].astype(np.float64))
             dx = np.minimum(dx, np.abs(Lbox - dx)).max()
             assert dx <= scale * self.band(), (self.name, dx, scale * self.band())
