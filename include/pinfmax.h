@@ -352,7 +352,9 @@ typedef struct { int start[3], len[3]; } pf_subbox;
 int pf_distribute(pf_ctx *ctx, double flast, const pf_subbox *sub, const unsigned int *map, const pf_product_layout *layout,
                   size_t capacity, void *frag, unsigned int *frag_pos, size_t *count);
 /* test tap without a context: the selection and ordering kernels on a caller's slab of an fp32 field -- planes x0 .. x0 + nxl - 1
-   of an n^3 box, host, index z + n*(y + n*x_local); returns frag_pos and the local cell index of each taken cell */
+   of an n^3 box, host, index z + n*(y + n*x_local); returns frag_pos and the local cell index of each taken cell.  n <= 2048; the
+   sub-box has at most 2^32 cells (frag_pos is 32-bit) and so has the slab: cell_index is 32-bit and holds the indices 0 .. 2^32 - 1,
+   the limit pf_group_velocity_sums sets for its keys (a slab of exactly 2^32 cells is accepted by both, one of 2^32 + 1 by neither) */
 int pf_debug_distribute(int n, int x0, int nxl, const float *fmax_host, double flast, const pf_subbox *sub, const unsigned int *map,
                         size_t capacity, unsigned int *frag_pos, unsigned int *cell_index, size_t *count);
 /* The call of fragment() (src/fragment.c:193-346) that follows distribute(): sort_and_organize() (:484-520).  The reference sorts

@@ -2356,7 +2356,8 @@ extern "C" int pf_debug_distribute(int n, int x0, int nxl, const float *fmax_hos
                                    size_t capacity, unsigned int *frag_pos, unsigned int *cell_index, size_t *count) {
   if (!fmax_host || !sub || !count || n < 1 || n > 2048 || nxl < 1 || x0 < 0 || x0 + nxl > n) return pf_fail(0, "pf_debug_distribute: bad argument");
   const size_t nc = (size_t)nxl * n * n;
-  if (nc > 0xFFFFFFFFull) return pf_fail(0, "pf_debug_distribute: more than 2^32 cells in the slab");
+  // cell_index is 32-bit: the cells 0 .. nc - 1 of a slab of up to 2^32 cells fit (the limit of the group-velocity keys, pf_groupvel.hip)
+  if (nc > 0x100000000ull) return pf_fail(0, "pf_debug_distribute: a slab of %zu cells: cell_index holds a cell index below 2^32", nc);
   PfDistTable t;
   if (pf_dist_table_checked(0, "pf_debug_distribute", n, x0, nxl, sub, &t)) return 1;
   PfDistScratch s;

@@ -10,6 +10,7 @@
 
 #include "../../pinocchio_amd/csrc/pf_distribute_boxes.h"
 #include "../../pinocchio_amd/csrc/pf_back_core.h"
+#include "large_boxes.h"
 
 static PfBackBox box_of(int n, int x0, int nxl, const int *start, const int *len, const int *safe) {
   PfBackBox b;
@@ -109,6 +110,31 @@ int main() {
       printf("n %d slab %d+%d box (%d %d %d)+(%d %d %d) form %d: stored %llu of %zu\n", cs.n, cs.x0, cs.nxl, cs.start[0], cs.start[1], cs.start[2], cs.len[0],
              cs.len[1], cs.len[2], form, s0, count);
     }
+  }
+  // the production-size boxes: positions up to 2^32 - 1 from a sparse set; two planes on the last x-planes of the sub-box from a start
+  // that wraps in all three directions, and the two planes that begin with position 2^31 from a straight start
+  for (const LargeBox &lb : LARGE_BOXES) {
+    const std::vector<unsigned int> pos = large_positions(lb.len, 200000, rnd);
+    const size_t count = pos.size(), ncell = (size_t)2 * lb.n * lb.n;
+    std::vector<float> zacc(count);
+    std::vector<int> gid(count);
+    for (size_t i = 0; i < count; i++) { zacc[i] = (float)(rnd() % 16777216); gid[i] = (rnd() % 5) ? (int)(rnd() & 0x7FFFFFFF) : 0; }
+    gid[0] = 0x7FFFFFFF;
+    const int zero[3] = {0, 0, 0};
+    unsigned long long kept[2];
+    for (int geo = 0; geo < 2; geo++) {
+      const int *start = geo ? zero : lb.wrapped;
+      const int x0 = geo ? large_mid_plane(lb.len) : (lb.wrapped[0] + lb.len[0] - 2) % lb.n;
+      std::vector<float> z0(ncell, -1.0f), z1(ncell, -1.0f);
+      std::vector<int> g0(ncell, 0), g1(ncell, 0);
+      const unsigned long long s0 = emul_back(lb.n, x0, 2, start, lb.len, lb.safe, count, pos.data(), zacc.data(), gid.data(), z0.data(), g0.data());
+      const unsigned long long s1 = port_back(lb.n, x0, 2, start, lb.len, lb.safe, count, pos.data(), zacc.data(), gid.data(), z1.data(), g1.data());
+      if (s0 != s1 || !s0) { printf("MISMATCH: large box %s: %llu kept, the port %llu\n", lb.name, s0, s1); return 1; }
+      for (size_t i = 0; i < ncell; i++)
+        if (!(z0[i] == z1[i]) || g0[i] != g1[i]) { printf("MISMATCH: large box %s at cell %zu\n", lb.name, i); return 1; }
+      kept[geo] = s0;
+    }
+    printf("large box %s n %d (%d %d %d): kept %llu on the last planes, %llu at 2^31, of %zu particles\n", lb.name, lb.n, lb.len[0], lb.len[1], lb.len[2], kept[0], kept[1], count);
   }
   return 0;
 }

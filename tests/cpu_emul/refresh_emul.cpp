@@ -12,6 +12,7 @@
 
 #include "../../pinocchio_amd/csrc/pf_distribute_boxes.h"
 #include "../../pinocchio_amd/csrc/pf_refresh_core.h"
+#include "large_boxes.h"
 
 static PfBackBox box_of(int n, int x0, int nxl, const int *start, const int *len, const int *safe) {
   PfBackBox b;
@@ -143,6 +144,31 @@ int main() {
       printf("n %d slab %d+%d box (%d %d %d)+(%d %d %d) form %d: found %llu of %zu\n", cs.n, cs.x0, cs.nxl, cs.start[0], cs.start[1], cs.start[2], cs.len[0],
              cs.len[1], cs.len[2], form, f0, count);
     }
+  }
+  // the production-size boxes: positions up to 2^32 - 1 from a sparse set; the last x-plane of the sub-box from a start that wraps in
+  // all three directions, and the plane of position 2^31 from a straight start; the particles' own order and a random one
+  for (const LargeBox &lb : LARGE_BOXES) {
+    const std::vector<unsigned int> pos = large_positions(lb.len, 200000, rnd);
+    const size_t count = pos.size(), ncell = (size_t)lb.n * lb.n;
+    std::vector<float> cols(24 * ncell);
+    for (size_t q = 0; q < 24 * ncell; q++) cols[q] = (float)(((unsigned int)q * 2654435761u) >> 8);
+    std::vector<int> order(count);
+    for (size_t i = 0; i < count; i++) order[i] = (int)i;
+    for (size_t i = count; i > 1; i--) { const size_t j = rnd() % i; const int t = order[i - 1]; order[i - 1] = order[j]; order[j] = t; }
+    const int zero[3] = {0, 0, 0};
+    unsigned long long hits[2];
+    for (int geo = 0; geo < 2; geo++) {
+      const int *start = geo ? zero : lb.wrapped;
+      const int x0 = geo ? large_mid_plane(lb.len) : (lb.wrapped[0] + lb.len[0] - 1) % lb.n;
+      std::vector<unsigned int> i0(count + 1, 0xDEADBEEFu), i1(count + 1, 0xDEADBEEFu);
+      std::vector<float> v0(24 * count + 1, -7.0f), v1(24 * count + 1, -7.0f);
+      const unsigned long long f0 = emul_gather(lb.n, x0, 1, start, lb.len, lb.safe, count, pos.data(), geo ? order.data() : nullptr, cols.data(), count, i0.data(), v0.data());
+      const unsigned long long f1 = port_gather(lb.n, x0, 1, start, lb.len, count, pos.data(), cols.data(), i1.data(), v1.data());
+      if (f0 != f1 || !f0) { printf("MISMATCH: large box %s: %llu hits, the port %llu\n", lb.name, f0, f1); return 1; }
+      if (i0 != i1 || v0 != v1) { printf("MISMATCH: large box %s: the entries differ\n", lb.name); return 1; }
+      hits[geo] = f0;
+    }
+    printf("large box %s n %d (%d %d %d): %llu hits on the last plane, %llu at 2^31, of %zu particles\n", lb.name, lb.n, lb.len[0], lb.len[1], lb.len[2], hits[0], hits[1], count);
   }
   return 0;
 }

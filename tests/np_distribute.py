@@ -120,6 +120,42 @@ def contribution(fmax_slab, n, x0, start, length, flast, words=None):
     return np.concatenate(cells), np.concatenate(where)
 
 
+def map_bits_at(words, pos):
+    """get_map_bit for the positions pos (int64, any shape) by word lookup: bit pos % 32 of word pos // 32 (None: every bit set)"""
+    pos = np.asarray(pos, dtype=np.int64)
+    if words is None:
+        return np.ones(pos.shape, dtype=bool)
+    w = np.asarray(words, dtype=np.uint32)
+    return ((w[pos >> 5] >> (pos & 31).astype(np.uint32)) & np.uint32(1)).astype(bool)
+
+
+def contribution_sparse(fmax_slab, n, x0, start, length, flast, words=None):
+    """contribution() without an array over the cells of the sub-box, for sub-boxes of up to 2^32 cells: every intersection box
+    carries its own coordinates -- global g = bstart .. bstart + blen - 1 per direction, sub-box coordinate p = (g - start) mod n,
+    position pz + Lz (py + Ly px) in int64 by broadcasting over the box -- and reads its map bits by word lookup.  Memory goes as
+    the cells of the slab, never as those of the sub-box.  -> (local cell index, frag_pos), int64, in the reference's order"""
+    slab = np.asarray(fmax_slab)
+    nxl = slab.shape[0]
+    assert slab.shape == (nxl, n, n)
+    length = [int(v) for v in length]
+    start = [int(v) for v in start]
+    cells, where = [], []
+    for bstart, blen in intersection(n, [x0, 0, 0, nxl, n, n], start + length):
+        g = [np.arange(bstart[d], bstart[d] + blen[d], dtype=np.int64) for d in range(3)]
+        p = [np.mod(g[d] - start[d], n) for d in range(3)]
+        assert all(p[d].max() < length[d] for d in range(3)), "an intersection box lies inside the sub-box"
+        pos = p[2][None, None, :] + length[2] * (p[1][None, :, None] + length[1] * p[0][:, None, None])
+        f = slab[bstart[0] - x0:bstart[0] - x0 + blen[0], bstart[1]:bstart[1] + blen[1], bstart[2]:bstart[2] + blen[2]].astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            take = map_bits_at(words, pos) & (f >= float(flast))
+        cell = g[2][None, None, :] + n * (g[1][None, :, None] + n * (g[0][:, None, None] - x0))
+        cells.append(np.broadcast_to(cell, take.shape)[take])      # boolean indexing walks in C order: x slowest, z fastest
+        where.append(pos[take])
+    if not cells:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    return np.concatenate(cells), np.concatenate(where)
+
+
 def hypercube_order(ntasks, target):
     """the tasks in the order their cells reach frag[] of `target`: itself (keep_data), then its partner of every round of the
     hypercube loop (:115-148: bit = 1 .. 2^ceil(log2 ntasks) - 1, partner = target ^ bit when that task exists)"""

@@ -5,6 +5,9 @@ A map is a boolean array [Lx][Ly][Lz] over subbox.Lgwbl here; words_of() packs i
 pos = z + Lz (y + Ly x), COORD_TO_INDEX, in word pos // 32, bit pos % 32, UINTLEN = 32).  Shares nothing with the device kernels
 or with pinocchio_amd/csrc/pf_map_core.h: the fill is three slices, a sphere is one np.ogrid expression per group, and the
 triple loop of the reference is kept beside it as update_map_loops() (tests/test_maps_cpu.py holds the two against each other).
+create_map_words / create_map_count / update_map_sparse are the same answers for sub-boxes of up to 2^32 cells, where no cube fits:
+words on request, the closed-form bit count, and the requested positions as a sorted int64 list (tests/test_large_index_cpu.py holds
+them against the dense forms).
 """
 import math
 
@@ -115,6 +118,89 @@ def update_map_loops(current, pos, mass, blf, pbc):
                             upd[i, j, k] = True
                             nadd[0] += 1
     return upd, (nadd[0], nadd[1])
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# sparse forms for sub-boxes of up to 2^32 cells: nothing here allocates per cell (or per word) of the sub-box
+def box_ranges(length, safe, pbc):
+    """create_map's range [lo, hi) per direction"""
+    lo = [0 if pbc[d] else int(safe[d]) - 1 for d in range(3)]
+    hi = [int(length[d]) if pbc[d] else int(length[d]) - int(safe[d]) + 1 for d in range(3)]
+    return lo, hi
+
+
+def in_ranges(pos, length, lo, hi):
+    """whether the bits at the positions pos (int64, any shape) lie in the box [lo, hi) of a map over `length`"""
+    pos = np.asarray(pos, dtype=np.int64)
+    ly, lz = int(length[1]), int(length[2])
+    c = (pos // (lz * ly), (pos // lz) % ly, pos % lz)
+    out = np.ones(pos.shape, dtype=bool)
+    for d in range(3):
+        out &= (c[d] >= lo[d]) & (c[d] < hi[d])
+    return out
+
+
+def create_map_words(length, safe, pbc, word_index):
+    """the words word_index (any order, int64) of words_of(create_map(length, safe, pbc)), from the per-direction ranges: bit b of word
+    w is position 32 w + b; positions beyond the last cell are zero"""
+    w = np.asarray(word_index, dtype=np.int64)
+    cells = int(length[0]) * int(length[1]) * int(length[2])
+    lo, hi = box_ranges(length, safe, pbc)
+    out = np.zeros(len(w), dtype=np.uint32)
+    for a in range(0, len(w), 1 << 18):                     # in pieces: 32 positions per word
+        pos = 32 * w[a:a + (1 << 18), None] + np.arange(32, dtype=np.int64)[None, :]
+        bit = in_ranges(np.minimum(pos, cells - 1), length, lo, hi) & (pos < cells)
+        out[a:a + (1 << 18)] = (bit.astype(np.uint32) << np.arange(32, dtype=np.uint32)[None, :]).sum(axis=1, dtype=np.uint32)
+    return out
+
+
+def create_map_count(length, safe, pbc):
+    """the bits create_map sets: the product of its three ranges"""
+    lo, hi = box_ranges(length, safe, pbc)
+    return (hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2])
+
+
+def update_map_sparse(current, length, pos, mass, blf, pbc):
+    """update_map() without the cube: current is None (an empty frag_map) or a function of an int64 position array that gives its
+    bits.  -> (the ascending int64 positions the groups request, (nadd0, nadd1), {word: mask} of the words of frag_map_update that
+    are not zero).  One np.ogrid expression per group, as update_map"""
+    L = [int(v) for v in length]
+    requested = []
+    nadd0 = nadd1 = 0
+    for g in range(len(mass)):
+        c, size = centre_and_size(pos[g], mass[g], blf)
+        if size <= 0:
+            continue
+        off = np.arange(-size, size, dtype=np.int64)
+        idx, ok = [], []
+        for d in range(3):
+            c1 = c[d] + off
+            inside = (c1 >= 0) & (c1 < L[d])
+            if pbc[d]:
+                w = np.where(c1 < 0, c1 + L[d], np.where(c1 >= L[d], c1 - L[d], c1))   # ONE wrap
+                assert np.all((w >= 0) & (w < L[d])), "the reference would index out of bounds"
+                idx.append(w)
+                ok.append(np.ones(len(off), dtype=bool))
+            else:
+                idx.append(np.where(inside, c1, 0))
+                ok.append(inside)
+        oi, oj, ok3 = np.ogrid[:2 * size, :2 * size, :2 * size]
+        valid = ok[0][oi] & ok[1][oj] & ok[2][ok3]
+        nadd1 += int(valid.size - valid.sum())
+        sphere = (off[oi] ** 2 + off[oj] ** 2 + off[ok3] ** 2) <= size * size
+        p = idx[2][ok3] + L[2] * (idx[1][oj] + L[1] * idx[0][oi])
+        cand = p[valid & sphere]
+        if current is not None:
+            cand = cand[~np.asarray(current(cand), dtype=bool)]
+        nadd0 += len(cand)
+        requested.append(cand)
+    allpos = np.unique(np.concatenate(requested)) if requested else np.zeros(0, dtype=np.int64)
+    words = {}
+    if len(allpos):
+        wi, first = np.unique(allpos >> 5, return_index=True)
+        masks = np.bitwise_or.reduceat(np.uint64(1) << (allpos & 31).astype(np.uint64), first)
+        words = {int(a): int(b) for a, b in zip(wi, masks)}
+    return allpos, (nadd0, nadd1), words
 
 
 def stored_mask(field, flast, box, mapbits):

@@ -16,6 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "cpu_emul", "map_emul.cpp")
 SO = os.path.join(HERE, "cpu_emul", "libmap_emul.so")
 EXE = os.path.join(HERE, "cpu_emul", "map_emul_san")
+LARGE = os.path.join(HERE, "cpu_emul", "large_boxes.h")      # the boxes the mains of the programs share
 HDR = os.path.join(HERE, "..", "pinocchio_amd", "csrc", "pf_map_core.h")
 
 # (len, safe, periodic directions)
@@ -27,7 +28,7 @@ BOXES = [((20, 23, 37), (4, 4, 4), (False, False, False)),
 
 
 def _stale(out):
-    return (not os.path.exists(out)) or os.path.getmtime(out) < max(os.path.getmtime(SRC), os.path.getmtime(HDR))
+    return (not os.path.exists(out)) or os.path.getmtime(out) < max(os.path.getmtime(SRC), os.path.getmtime(HDR), os.path.getmtime(LARGE))
 
 
 @pytest.fixture(scope="module")

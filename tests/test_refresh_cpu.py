@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "cpu_emul", "refresh_emul.cpp")
 SO = os.path.join(HERE, "cpu_emul", "librefresh_emul.so")
 EXE = os.path.join(HERE, "cpu_emul", "refresh_emul_san")
+LARGE = os.path.join(HERE, "cpu_emul", "large_boxes.h")      # the boxes the mains of the programs share
 HDRS = [os.path.join(HERE, "..", "pinocchio_amd", "csrc", h) for h in ("pf_refresh_core.h", "pf_back_core.h", "pf_neigh_core.h", "pf_distribute_boxes.h")]
 
 # (n, start, len, safe): the boxes of tests/test_gpu_refresh.py -- the whole periodic box; wraps in x and z with y periodic; two
@@ -87,7 +88,7 @@ def test_the_scatter_into_records():
 # ------------------------------------------------------------------------------------------------------------------------
 # the host compilation of the device path's arithmetic
 def _stale(out):
-    return (not os.path.exists(out)) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in [SRC] + HDRS)
+    return (not os.path.exists(out)) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in [SRC, LARGE] + HDRS)
 
 
 @pytest.fixture(scope="module")
