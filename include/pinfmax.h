@@ -750,6 +750,54 @@ int pf_catalog(pf_ctx *ctx, const pf_plc_segment *seg, const pf_peak_region *box
                const pf_mf_bins *bins, int *ninbin, double *massinbin, size_t *count);
 int pf_debug_catalog_times(double *ms2);
 int pf_debug_catalog_parts(double *ms4);
+/* --- the state of every stored particle at its own collapse time (src/build_groups.c:1286-1317 and what it calls) ---
+   condition_for_accretion() evaluates, for the particle iz the loop of build_groups() works on, virial(Mass, F, flag) (:1023-1051),
+   set_point(i, j, k, ind, F, ...) (:1464-1520) with its set_weight() (:1411-1444) and, through distance() (:1646-1664), q2x()
+   (:1554-1603) of the point -- all at F = frag[iz].Fmax, once per neighbouring group and once more per filament particle.  What of
+   this depends on F, the particle's cell and its velocities alone -- not on the sequential group state -- is computed here for a
+   whole batch of stored particles from the columns in HBM; the host loop then reads a table.
+   box, frag_pos, order, capacity, index and found follow the contract of pf_gather_velocities to the letter: the cell of a
+   particle, FOUND by slab, ascending i, *found counting beyond capacity, periodic when len[d] == n, duplicates legal, an order
+   that is no permutation omits particles (index 0xFFFFFFFF, zero values), NOT collective.  `order` is the access hint of that
+   call; it has nothing to do with par->order.
+   seg: as in pf_plc_cross (myseg, z_seg = ScaleDep.z[myseg], z_prev = ScaleDep.z[myseg - 1] read when myseg >= 1; use_v31 = 0
+   reproduces :1588 as written).
+   par: sigma0 = sqrt(Smoothing.TrueVariance[Nsmooth - 1]); k_sigma = Smoothing.k_GM_dens[Nsmooth - 1] in a -DSCALE_DEPENDENT build,
+   else params.k_for_GM (:1040-1045); k_point = Smoothing.k_GM_displ[Nsmooth - 1], else params.k_for_GM (:1470-1475); order =
+   ORDER_FOR_GROUPS (2), 1 to 3; the order q2x uses is min(order, the order of pf_set_lpt_order).
+   states: 8 PRODFLOATs per found particle, entry j beside index[j].  With F the PRODFLOAT in the Fmax column of the particle's
+   cell and z = (double)F - 1.0:
+     [0..3]  w, w2, w31, w32 of set_weight() for myk = k_point -- the branch of myseg == 0 or of myseg >= 1 --, each rounded to
+             PRODFLOAT where the reference's assignment rounds; GrowingMode_3LPT_1 keeps its minus sign (cosmo.c:1810); the slots
+             of LPT orders the context does not compute (pf_set_lpt_order) are zero
+     [4]     sigmaD of virial(): (PRODFLOAT)(sigma0 * GrowingMode(z, k_sigma))
+     [5..7]  q2x(d, point, pbc[d], (double)Lgwbl[d], order) for d = 0..2 with q[d] = the sub-box coordinate + SHIFT (0.5), the
+             velocities from the current columns and, for myseg >= 1, from the prev columns; the two periodic wraps in the
+             reference's order (>= Box first, then < 0)
+   It reads the growth tables of pf_plc_set_cosmology (pf_plc_set_geometry need not have been called).  With nk == 1 there is one
+   table per family and the two k values are not read; with nk > 1 each goes through the three branches of InterpolateGrowth
+   (cosmo.c:1737-1749).  Only the tables the call reads are staged on the CU: with nk > 1 the two bins around k_point of the four
+   growth families and those around k_sigma of the first.  The growing modes at the segment's redshifts are computed once per call.
+   Deterministic: no floating-point atomics; output identical from run to run and with or without `order`.
+   4 bytes go up per particle, 8 with order; 4 + 8 PRODFLOATs come down per found particle.  When the scratch cannot be allocated
+   the call says how many bytes it needs.
+   Refused (return 1, pf_last_error, *found = 0) before anything is launched: null arguments; no cosmology set; no products;
+   myseg >= 1 without prev columns; myseg < 0; par->order outside 1..3; sigma0, k_sigma or k_point not finite or <= 0; a bad box; a
+   frag_pos entry not below Lx Ly Lz or an order entry not below count (the first offender named); 2^31 particles or more.
+   pf_debug_point_states: test tap on a caller's host columns: planes x0 .. x0 + nxl - 1 of an n^3 box, pb = 4 or 8; fmax_col =
+   nxl n n values, cols24 as for pf_debug_gather_velocities; tables_ctx supplies the cosmology tables and nothing else; the LPT
+   order of the columns counts as 3; index and states have room for count entries.
+   pf_debug_point_times: with PF_POINT_TIMES=1 in the environment a call measures its device part between events; ms2 = the device
+   ms of the last call's select + scan passes and of its state pass.  Zeros otherwise.  For profiles/tools/points_time.py. */
+typedef struct { double sigma0, k_sigma, k_point; int order; } pf_point_params;
+int pf_point_states(pf_ctx *ctx, const pf_plc_segment *seg, const pf_peak_region *box, const pf_point_params *par,
+                    size_t count, const unsigned int *frag_pos, const int *order,
+                    size_t capacity, unsigned int *index, void *states, size_t *found);
+int pf_debug_point_states(int n, int x0, int nxl, int pb, const void *fmax_col, const void *cols24,
+                          pf_ctx *tables_ctx, const pf_plc_segment *seg, const pf_peak_region *box, const pf_point_params *par,
+                          size_t count, const unsigned int *frag_pos, const int *order,
+                          unsigned int *index, void *states, size_t *found);
+int pf_debug_point_times(double *ms2);
 /* Per-particle payload of one block of the "timeless snapshot" (write_timeless_snapshot, src/write_snapshot.c:207-342)
    for this rank's slab, from the SoA columns in HBM: name = "ID  " (1 + global index as MYIDTYPE of id_bytes = 4 or 8,
    :648-664), "FMAX" float, "RMAX" int, "ZEL " / "2LPT" / "31PT" / "32PT" float[3] per particle (:700-855), and the last

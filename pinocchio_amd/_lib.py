@@ -113,6 +113,10 @@ class MfBins(C.Structure):
     _fields_ = [("nbin", C.c_int), ("mmin", C.c_double), ("deltam", C.c_double)]
 
 
+class PointParams(C.Structure):
+    _fields_ = [("sigma0", C.c_double), ("k_sigma", C.c_double), ("k_point", C.c_double), ("order", C.c_int)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -228,6 +232,11 @@ PROTOTYPES = {
                              C.POINTER(CatalogOutLayout), C.POINTER(C.c_uint), C.POINTER(MfBins), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_size_t)]),
     "pf_debug_catalog_times": (C.c_int, [C.POINTER(C.c_double)]),
     "pf_debug_catalog_parts": (C.c_int, [C.POINTER(C.c_double)]),
+    "pf_point_states": (C.c_int, [_vp, C.POINTER(PlcSegment), C.POINTER(PeakRegion), C.POINTER(PointParams), C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_int),
+                                  C.c_size_t, C.POINTER(C.c_uint), _vp, C.POINTER(C.c_size_t)]),
+    "pf_debug_point_states": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.POINTER(PlcSegment), C.POINTER(PeakRegion), C.POINTER(PointParams),
+                                        C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_int), C.POINTER(C.c_uint), _vp, C.POINTER(C.c_size_t)]),
+    "pf_debug_point_times": (C.c_int, [C.POINTER(C.c_double)]),
     "pf_set_collapse_model": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "pf_set_modified_gravity": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
     "pf_set_tabulated_ct": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_double)]),

@@ -75,6 +75,13 @@ def catalog_parts():
     return tuple(float(x) for x in ms)
 
 
+def point_times():
+    """device ms of the last point_states: (select + scan passes, state pass); zeros without PF_POINT_TIMES=1 (pf_debug_point_times)"""
+    ms = (C.c_double * 2)()
+    _lib.load().pf_debug_point_times(ms)
+    return float(ms[0]), float(ms[1])
+
+
 def debug_peaks(fmax: np.ndarray, flast: float, region=None):
     """count_peaks (src/fragment.c:605-706) by the device kernel on a caller's [n][n][n] fp32 field -> (npeaks, ngood)"""
     L = _lib.load()
@@ -262,6 +269,35 @@ def debug_gather_velocities(n: int, x0: int, cols24: np.ndarray, box, frag_pos, 
                                     vel.ctypes.data_as(C.c_void_p), C.byref(found)):
         raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_gather_velocities failed")
     return index[:found.value], vel[:found.value]
+
+
+def debug_point_states(n: int, x0: int, fmax_col: np.ndarray, cols24: np.ndarray, tables, myseg, z_seg, box, frag_pos, sigma0, k_sigma, k_point, groups_order=2,
+                       z_prev=0.0, use_v31=False, order=None):
+    """the particle states of pf_point_states by the device kernel on a caller's columns (pf_debug_point_states): fmax_col [nxl n n]
+    and cols24 [24][nxl n n] (as debug_gather_velocities takes them) of one dtype, float32 or float64, for the slab planes x0 ..
+    x0 + nxl - 1 of an n^3 box; tables: an Fmax whose plc_set_cosmology supplies the growth tables and nothing else; groups_order =
+    par->order (ORDER_FOR_GROUPS); order: None or indices[] of sort_and_organize -> (index[found], states[found][8])"""
+    L = _lib.load()
+    cols = np.ascontiguousarray(cols24)
+    if cols.dtype not in (np.float32, np.float64):
+        cols = cols.astype(np.float32)
+    fm = np.ascontiguousarray(fmax_col, dtype=cols.dtype).ravel()
+    if cols.ndim != 2 or cols.shape[0] != 24 or cols.shape[1] % (int(n) * int(n)) or fm.size != cols.shape[1]:
+        raise ValueError(f"columns of shapes {fm.shape} and {cols.shape} for slab planes of {n} x {n} cells")
+    nxl = cols.shape[1] // (int(n) * int(n))
+    pos = np.ascontiguousarray(frag_pos, dtype=np.uint32).ravel()
+    o, op = _order(order, pos.size)
+    index = np.empty(pos.size, dtype=np.uint32)
+    st = np.empty((pos.size, 8), dtype=cols.dtype)
+    found = C.c_size_t()
+    rg = _region(box)
+    seg = _lib.PlcSegment(int(myseg), int(bool(use_v31)), float(z_seg), float(z_prev))
+    par = _lib.PointParams(float(sigma0), float(k_sigma), float(k_point), int(groups_order))
+    if L.pf_debug_point_states(int(n), int(x0), nxl, cols.dtype.itemsize, fm.ctypes.data_as(C.c_void_p), cols.ctypes.data_as(C.c_void_p), tables.h, C.byref(seg),
+                               C.byref(rg), C.byref(par), pos.size, pos.ctypes.data_as(C.POINTER(C.c_uint)), op, index.ctypes.data_as(C.POINTER(C.c_uint)),
+                               st.ctypes.data_as(C.c_void_p), C.byref(found)):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_point_states failed")
+    return index[:found.value], st[:found.value]
 
 
 def group_layout(stride, off_Mass=-1, off_Vel=-1, off_Vel_2LPT=-1, off_Vel_3LPT_1=-1, off_Vel_3LPT_2=-1, off_Vel_prev=-1, off_Vel_2LPT_prev=-1,
@@ -955,6 +991,28 @@ class Fmax:
                                             int(ngroups), C.byref(group_layout) if group_layout is not None else None, C.byref(loose), C.byref(grouped),
                                             C.byref(mism)))
         return int(loose.value), int(grouped.value), int(mism.value)
+
+    def point_states(self, myseg, z_seg, box, frag_pos, sigma0, k_sigma, k_point, groups_order=2, z_prev=0.0, use_v31=False, order=None, capacity=None):
+        """what condition_for_accretion() evaluates for a stored particle at its own collapse time, for the particles at the sub-box
+        positions frag_pos of the sub-box box = (start, length, safe) whose cells lie in this rank's slab (pf_point_states) ->
+        (index, states, found): index[j] = the particle, ascending; states[j] = w, w2, w31, w32 of set_weight(), sigmaD of virial()
+        and q2x() of the three axes, in the context's product precision, at F = the Fmax of the particle's cell.  sigma0 =
+        sqrt(TrueVariance[Nsmooth - 1]); k_sigma, k_point: the k of virial() and of set_point(); groups_order = par->order
+        (ORDER_FOR_GROUPS).  order: None or indices[] of sort_and_organize (same result; another access pattern on the device).
+        capacity: at most so many entries come back (found counts on).  Needs plc_set_cosmology.  Not collective."""
+        pos = np.ascontiguousarray(frag_pos, dtype=np.uint32).ravel()
+        o, op = _order(order, pos.size)
+        cap = pos.size if capacity is None else int(capacity)
+        index = np.empty(cap, dtype=np.uint32)
+        st = np.empty((cap, 8), dtype=self._zacc_dtype)
+        found = C.c_size_t()
+        rg = _region(box)
+        seg = _lib.PlcSegment(int(myseg), int(bool(use_v31)), float(z_seg), float(z_prev))
+        par = _lib.PointParams(float(sigma0), float(k_sigma), float(k_point), int(groups_order))
+        self._chk(self.L.pf_point_states(self.h, C.byref(seg), C.byref(rg), C.byref(par), pos.size, pos.ctypes.data_as(C.POINTER(C.c_uint)), op, cap,
+                                         index.ctypes.data_as(C.POINTER(C.c_uint)), st.ctypes.data_as(C.c_void_p), C.byref(found)))
+        m = min(int(found.value), cap)
+        return index[:m], st[:m], int(found.value)
 
     def plc_set_cosmology(self, x, comvdist, hubble, grow, fomega, k_for_GM=0.0, logkmin=-3.0, deltalogk=0.5, rad_gm0=0.0, k_gm_displ=None):
         """the splines the light-cone test reads (pf_plc_set_cosmology), all at the knots x = -log10(1 + z): comvdist, hubble [n];

@@ -355,6 +355,8 @@ size_t pf_refresh_in_bytes(size_t count, bool with_order);
 int pf_refresh_alloc_in(PfRefreshScratch *s, size_t count, bool with_order);
 int pf_refresh_alloc_out(PfRefreshScratch *s, size_t m, int pb, bool want_index, bool want_vel);
 int pf_refresh_scan(const unsigned int *counts, size_t nblocks, unsigned long long *offs, hipStream_t st);   // k_refresh_scan
+// k_refresh_flag + k_refresh_scan behind positions that lie on the device (pf_points.hip); synchronises the stream: *found sizes what follows
+int pf_refresh_select(const char *who, int task, const PfBackBox &b, size_t count, const PfRefreshScratch &s, hipStream_t st, unsigned long long *found);
 int pf_refresh_gather(int pb, const PfBackBox &b, size_t count, const PfRefreshScratch &s, const PfRefreshCols &cols, unsigned long long cap, hipStream_t st);
 int pf_refresh_box(const char *who, int rank, int n, int x0, int nxl, const pf_peak_region *box, PfBackBox *b, unsigned long long *cells);
 size_t pf_refresh_first_bad(const unsigned int *a, size_t upto, unsigned long long limit);

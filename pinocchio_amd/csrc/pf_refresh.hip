@@ -443,6 +443,9 @@ int pf_refresh_scan(const unsigned int *counts, size_t nblocks, unsigned long lo
   hipLaunchKernelGGL(k_refresh_scan, dim3(1), dim3(1024), 0, st, counts, (unsigned long long)nblocks, offs);
   return hipGetLastError() != hipSuccess;
 }
+int pf_refresh_select(const char *who, int task, const PfBackBox &b, size_t count, const PfRefreshScratch &s, hipStream_t st, unsigned long long *found) {
+  return refresh_select(who, task, b, count, s, st, found);
+}
 int pf_refresh_gather(int pb, const PfBackBox &b, size_t count, const PfRefreshScratch &s, const PfRefreshCols &cols, unsigned long long cap, hipStream_t st) {
   return refresh_gather(pb, b, count, s, cols, cap, st);
 }
