@@ -885,6 +885,62 @@ int pf_invgrow_table_status(pf_ctx *ctx, int ismooth, double *max_rel_err);
 /* per-cell solver on a list of Hessians d[6*count] -> F[count] (tests of
    inverse_collapse_time, src/collapse_times.c:679-776), ismooth selects the spline */
 int pf_collapse_cells(pf_ctx *ctx, int ismooth, const double *d, size_t count, double *F);
+/* The arithmetic of the collapse solve as a run-time setting of the context.  PF_ARITH_FAST: the series, table and hardware-seeded
+   forms of cos, acos, pow, log10, exp, / and sqrt, the default; PF_ARITH_EXACT: the reference's own calls.
+   The initial value is what PF_EXACT_LIBM says when pf_create runs.  pf_set_arithmetic holds for every solve that follows --
+   pf_sweep, pf_collapse_times, pf_collapse_cells, pf_ct_build -- and a context computes after it, bit for bit, what a context
+   created under the matching environment value computes: both solve kernels are compiled in and chosen at launch, the
+   polynomial tables of pf_set_invgrow are built whatever the flavour and read by the fast one alone (pf_invgrow_table_status
+   follows the setting), and neither the spline look-up, the solve queue's use nor the solve-beside-z-pass choice is decided by
+   anything kept from the flavour before.  A collapse-time table that pf_ct_build or a sweep built on the device belongs to the
+   flavour that built it: a change of flavour marks it as not in place, so that the next pf_collapse_times (or sweep) of its
+   radius rebuilds it from the variance it was built with.  A table installed by pf_ct_load is data and stays.
+   pf_set_arithmetic: 1 (pf_last_error) for a null context or a flavour that is neither; pf_get_arithmetic: -1 for a null context. */
+enum { PF_ARITH_FAST = 0, PF_ARITH_EXACT = 1 };
+int pf_set_arithmetic(pf_ctx *ctx, int flavour);
+int pf_get_arithmetic(pf_ctx *ctx);
+/* The census of a sweep: Fmax and Rmax of both flavours on the same resident delta(k), compared on the device.
+   A DIAGNOSTIC call: it costs two sweeps and one streaming pass over four columns.  It runs pf_sweep once in the other flavour,
+   keeps that sweep's Fmax / Rmax as shadow columns (product bytes + 4 per cell of the slab, allocated for the call and freed
+   before it returns, not counted in pf_device_bytes; when they do not fit the call fails before the first sweep and the
+   context is untouched), then pf_sweep in the context's own flavour, then the census kernel (csrc/pf_census.hip).  On return the
+   context is in exactly the state a plain pf_sweep(ctx, ns, radius_cells, true_variance) in its own flavour leaves: products,
+   true_variance, the sources of pf_set_sources_in_sweep, every flag, pf_device_bytes and the arithmetic setting.  Collective
+   exactly as pf_sweep is; it adds no communication: the numbers are this rank's, over its slab (summing counts and taking
+   maxima over ranks is the caller's).  pf_kernel_stats / pf_get_cputime show both sweeps.  It compares the two device flavours
+   on the device's own Hessian; it is no comparison with the reference's transforms.
+   Per cell, the same for float and double products: d = |fast - exact| formed in double; ulp = the spacing of
+   max(|exact|, 1) in the product precision, from its exponent bits; u = d / ulp.  hist[0]: u == 0 (identical bits, whatever
+   the value, and +0 against -0); hist[1]: 0 < u <= 1; hist[k], k >= 2: 2^(k-2) < u <= 2^(k-1); the last bin is open at the
+   top.  A cell whose bit patterns differ and where either side is NaN or infinite counts in `nonfinite` and nowhere in the
+   histogram or the maxima.  sum(hist) + nonfinite == cells.  max_abs / max_ulps: the largest d / u; max_abs_cell: the lowest
+   cell index that attains max_abs (all ones when every cell is nonfinite).  Cell index: z + n (y + n x_local).
+   The outlier records -- cells with d > 2 ulp or counted in nonfinite -- come in ascending cell index, the same from run to
+   run; the first min(outliers, capacity) are written.  cells may be NULL with capacity 0.  `fast` / `exact` always mean those
+   flavours, whichever ran last.  Integer sums and per-workgroup partials throughout: no floating-point atomics, the result
+   does not depend on the schedule.
+   Refused (1, pf_last_error) with the context untouched: null ctx / radius_cells / out, cells NULL with capacity > 0, ns
+   outside [1, PF_MAX_SMOOTH], no density set, no room for the shadow columns.
+   pf_debug_census: test tap without a context, the production kernels on a caller's host columns of `count` cells
+   (product_bytes 4: float, 8: double); the cell indices start at first_cell. */
+#define PF_CENSUS_BINS 64
+typedef struct {
+  unsigned long long cells;            /* cells of this rank's slab */
+  unsigned long long differing_bits;   /* Fmax bit patterns differ (+0 against -0 counts here and in bin 0) */
+  unsigned long long hist[PF_CENSUS_BINS];
+  unsigned long long beyond_2ulp;      /* = sum of hist[3..]: d > 2 ulp */
+  unsigned long long rmax_differing;
+  unsigned long long nonfinite;        /* either Fmax is NaN or infinite, and the bit patterns differ */
+  unsigned long long outliers;         /* beyond_2ulp + nonfinite: how many records exist, whatever the capacity */
+  double max_abs, max_ulps;            /* over the finite cells */
+  unsigned long long max_abs_cell;     /* lowest cell index that attains max_abs */
+} pf_census;
+typedef struct { unsigned long long cell; double fast, exact; int rmax_fast, rmax_exact; } pf_census_cell;   /* 32 bytes */
+int pf_flavour_census(pf_ctx *ctx, int ns, const double *radius_cells, double *true_variance,
+                      pf_census *out, size_t capacity, pf_census_cell *cells);
+int pf_debug_census(int product_bytes, unsigned long long first_cell, size_t count,
+                    const void *fmax_fast, const int *rmax_fast, const void *fmax_exact, const int *rmax_exact,
+                    pf_census *out, size_t capacity, pf_census_cell *cells);
 
 /* --- measurement --- */
 int pf_get_cputime(pf_ctx *ctx, pf_cputime *t);

@@ -117,6 +117,20 @@ class PointParams(C.Structure):
     _fields_ = [("sigma0", C.c_double), ("k_sigma", C.c_double), ("k_point", C.c_double), ("order", C.c_int)]
 
 
+ARITH_FAST, ARITH_EXACT = 0, 1   # PF_ARITH_*
+CENSUS_BINS = 64
+
+
+class Census(C.Structure):
+    _fields_ = [("cells", C.c_ulonglong), ("differing_bits", C.c_ulonglong), ("hist", C.c_ulonglong * CENSUS_BINS), ("beyond_2ulp", C.c_ulonglong),
+                ("rmax_differing", C.c_ulonglong), ("nonfinite", C.c_ulonglong), ("outliers", C.c_ulonglong), ("max_abs", C.c_double),
+                ("max_ulps", C.c_double), ("max_abs_cell", C.c_ulonglong)]
+
+
+class CensusCell(C.Structure):
+    _fields_ = [("cell", C.c_ulonglong), ("fast", C.c_double), ("exact", C.c_double), ("rmax_fast", C.c_int), ("rmax_exact", C.c_int)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -270,6 +284,11 @@ PROTOTYPES = {
     "pf_forward_transform": (C.c_int, [_vp, _dp, _dp]),
     "pf_reverse_transform": (C.c_int, [_vp, _dp, _dp]),
     "pf_collapse_cells": (C.c_int, [_vp, C.c_int, _dp, C.c_size_t, _dp]),
+    "pf_set_arithmetic": (C.c_int, [_vp, C.c_int]),
+    "pf_get_arithmetic": (C.c_int, [_vp]),
+    "pf_flavour_census": (C.c_int, [_vp, C.c_int, _dp, _dp, C.POINTER(Census), C.c_size_t, C.POINTER(CensusCell)]),
+    "pf_debug_census": (C.c_int, [C.c_int, C.c_ulonglong, C.c_size_t, _vp, C.POINTER(C.c_int), _vp, C.POINTER(C.c_int), C.POINTER(Census), C.c_size_t,
+                                  C.POINTER(CensusCell)]),
     "pf_get_cputime": (C.c_int, [_vp, C.POINTER(CpuTime)]),
     "pf_reset_cputime": (C.c_int, [_vp]),
     "pf_kernel_stats": (C.c_int, [_vp, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),

@@ -82,6 +82,58 @@ def point_times():
     return float(ms[0]), float(ms[1])
 
 
+_ARITH = {"fast": _lib.ARITH_FAST, "exact": _lib.ARITH_EXACT}
+# pf_census_cell: an outlier of the flavour census
+CENSUS_CELL_DTYPE = np.dtype([("cell", "<u8"), ("fast", "<f8"), ("exact", "<f8"), ("rmax_fast", "<i4"), ("rmax_exact", "<i4")], align=False)
+_CENSUS_COUNTS = ("cells", "differing_bits", "beyond_2ulp", "rmax_differing", "nonfinite", "outliers")
+
+
+def _census_dict(c):
+    d = {k: int(getattr(c, k)) for k in _CENSUS_COUNTS}
+    d["hist"] = np.array(c.hist[:], dtype=np.uint64)
+    d["max_abs"], d["max_ulps"], d["max_abs_cell"] = float(c.max_abs), float(c.max_ulps), int(c.max_abs_cell)
+    return d
+
+
+def debug_census(fmax_fast, rmax_fast, fmax_exact, rmax_exact, first_cell: int = 0, capacity: int = 1024):
+    """the census kernels on a caller's columns (pf_debug_census): Fmax columns of one dtype, float32 or float64, Rmax int32; the
+    cell indices start at first_cell -> (census dict, outlier records as CENSUS_CELL_DTYPE)"""
+    L = _lib.load()
+    ff, fe = np.ascontiguousarray(fmax_fast), np.ascontiguousarray(fmax_exact)
+    if ff.dtype != fe.dtype or ff.dtype not in (np.float32, np.float64):
+        raise ValueError(f"Fmax columns of {ff.dtype} and {fe.dtype}")
+    rf, re = np.ascontiguousarray(rmax_fast, dtype=np.int32), np.ascontiguousarray(rmax_exact, dtype=np.int32)
+    if not (ff.shape == fe.shape == rf.shape == re.shape and ff.ndim == 1):
+        raise ValueError("four columns of one length")
+    out = _lib.Census()
+    capacity = int(capacity)
+    rec = np.zeros(max(capacity, 1), dtype=CENSUS_CELL_DTYPE)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    if L.pf_debug_census(ff.dtype.itemsize, int(first_cell), len(ff), ff.ctypes.data_as(C.c_void_p), ip(rf), fe.ctypes.data_as(C.c_void_p), ip(re),
+                         C.byref(out), capacity, rec.ctypes.data_as(C.POINTER(_lib.CensusCell)) if capacity else None):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_census failed")
+    cen = _census_dict(out)
+    return cen, rec[:min(cen["outliers"], capacity)].copy()
+
+
+def census_sum(parts):
+    """the census of a box from those of its ranks, in rank order: counts and histogram summed, maxima taken.  max_abs_cell becomes
+    an index of the whole box -- a rank's cells follow those of the ranks before it --, of the first rank that attains max_abs"""
+    parts = list(parts)
+    tot = {k: sum(p[k] for p in parts) for k in _CENSUS_COUNTS}
+    tot["hist"] = np.sum([np.asarray(p["hist"], dtype=np.uint64) for p in parts], axis=0, dtype=np.uint64)
+    tot["max_abs"], tot["max_ulps"], tot["max_abs_cell"] = 0.0, 0.0, 2 ** 64 - 1
+    before = 0
+    for p in parts:
+        none = p["max_abs_cell"] == 2 ** 64 - 1   # every cell of that rank is nonfinite
+        if not none and (tot["max_abs_cell"] == 2 ** 64 - 1 or p["max_abs"] > tot["max_abs"]):
+            tot["max_abs"], tot["max_abs_cell"] = p["max_abs"], before + p["max_abs_cell"]
+        if not none:
+            tot["max_ulps"] = max(tot["max_ulps"], p["max_ulps"])
+        before += p["cells"]
+    return tot
+
+
 def debug_peaks(fmax: np.ndarray, flast: float, region=None):
     """count_peaks (src/fragment.c:605-706) by the device kernel on a caller's [n][n][n] fp32 field -> (npeaks, ngood)"""
     L = _lib.load()
@@ -1211,6 +1263,31 @@ class Fmax:
         out = np.empty(len(d))
         self._chk(self.L.pf_collapse_cells(self.h, ismooth, _dp(d), len(d), _dp(out)))
         return out
+
+    def set_arithmetic(self, flavour: str):
+        """"fast" (the default forms of the solve's elementary functions) or "exact" (the reference's calls) for every solve that
+        follows; a context computes after it what one created under the matching PF_EXACT_LIBM computes (pf_set_arithmetic)"""
+        if flavour not in _ARITH:
+            raise ValueError(f'flavour {flavour!r}: "fast" or "exact"')
+        self._chk(self.L.pf_set_arithmetic(self.h, _ARITH[flavour]))
+
+    @property
+    def arithmetic(self) -> str:
+        return "exact" if self.L.pf_get_arithmetic(self.h) == _lib.ARITH_EXACT else "fast"
+
+    def flavour_census(self, radii_cells, capacity: int = 1024):
+        """the sweep in both flavours on the resident density, compared on the device (pf_flavour_census; a diagnostic: two sweeps
+        and a pass) -> (TrueVariance[], census dict, the first min(outliers, capacity) outlier records as CENSUS_CELL_DTYPE in
+        ascending cell index).  The context is left as a plain sweep in its own flavour leaves it."""
+        r = np.ascontiguousarray(radii_cells, dtype=np.float64)
+        tv = np.zeros(len(r))
+        out = _lib.Census()
+        capacity = int(capacity)
+        rec = np.zeros(max(capacity, 1), dtype=CENSUS_CELL_DTYPE)
+        self._chk(self.L.pf_flavour_census(self.h, len(r), _dp(r), _dp(tv), C.byref(out), capacity,
+                                           rec.ctypes.data_as(C.POINTER(_lib.CensusCell)) if capacity else None))
+        cen = _census_dict(out)
+        return tv, cen, rec[:min(cen["outliers"], capacity)].copy()
 
     # -- measurement ------------------------------------------------------
     def cputime(self) -> dict:

@@ -186,6 +186,7 @@ struct pf_ctx {
   double tab_var[PF_MAX_SMOOTH];
   bool tab_ready;
   int tab_ismooth;
+  int tab_built_fast;  // the table in place was built on the device by the fast (1) / exact (0) flavour; -1: the caller's (pf_ct_load), or none
   int model;           // 0 ELL_CLASSIC, 1 ELL_SNG (fills the collapse-time table of a TABULATED_CT build; per cell without one)
   double sng_cosmo[7], sng_Din[PF_MAX_SMOOTH], sng_size[PF_MAX_SMOOTH];
   int sng_ns;
@@ -545,7 +546,7 @@ extern "C" int pf_create(pf_ctx **out, const pf_config *cfg) {
   c->pipeline = c->P > 1 && tune.pipeline;
   for (int i = 0; i < 3; i++) { c->A[i] = nullptr; c->S[i] = nullptr; }
   memset(c->gt_n, 0, sizeof(c->gt_n));
-  c->tab_ns = 0; c->tab_ready = false; c->tab_ismooth = -1; c->model = 0; c->sng_ns = 0; memset(c->sng_cosmo, 0, sizeof(c->sng_cosmo)); memset(c->sng_size, 0, sizeof(c->sng_size)); memset(&c->ct, 0, sizeof(c->ct));
+  c->tab_ns = 0; c->tab_ready = false; c->tab_ismooth = -1; c->tab_built_fast = -1; c->model = 0; c->sng_ns = 0; memset(c->sng_cosmo, 0, sizeof(c->sng_cosmo)); memset(c->sng_size, 0, sizeof(c->sng_size)); memset(&c->ct, 0, sizeof(c->ct));
   const int rc = create_body(c, cfg);
   if (rc) {  // nothing of a half-built context stays behind (13 fields of 8.7 GB each at 1024^3)
     std::string msg = g_err;
@@ -1459,6 +1460,7 @@ static int ct_build(pf_ctx *c, int ismooth, double variance, const double *table
     PFCHK(c, pf_launch_ct_build(sp, c->ct, c->fast_libm ? 1 : 0, table_host ? 0 : 1, st));
   }
   c->tab_ready = true; c->tab_ismooth = ismooth;
+  c->tab_built_fast = table_host ? -1 : (c->fast_libm ? 1 : 0);
   return 0;
 }
 extern "C" int pf_set_collapse_model(pf_ctx *c, int model, const double cosmo[4], int nsmooth, const double *D_in) {
@@ -1752,6 +1754,51 @@ extern "C" int pf_sweep(pf_ctx *c, int ns, const double *radius_cells, double *t
   // field do not raise the flag; the flag is summed over the ranks with the variances, so all of them repeat together.)
   if (rc == 2) { c->inv_reruns++; rc = sweep_body(c, ns, radius_cells, true_variance, true); }
   return rc;
+}
+// ---- the arithmetic of the solve as a setting; the census of a sweep under both (kernels: pf_census.hip) ----
+// Nothing but fast_libm remembers the flavour -- the polynomial tables of pf_set_invgrow exist either way and the launches pick the
+// kernels by p.fast -- except a collapse-time table built on the device: that one is marked as not in place, so that its radius is
+// rebuilt (from tab_var, which pf_ct_build recorded) by whoever needs it next.  A caller's table (pf_ct_load) is data and stays.
+static void arithmetic_set(pf_ctx *c, bool fast) {
+  if (c->fast_libm == fast) return;
+  c->fast_libm = fast;
+  if (c->tab_ready && c->tab_built_fast >= 0) c->tab_ready = false;
+}
+extern "C" int pf_set_arithmetic(pf_ctx *c, int flavour) {
+  if (!c) return pf_fail(0, "pf_set_arithmetic: null argument");
+  if (flavour != PF_ARITH_FAST && flavour != PF_ARITH_EXACT)
+    return pf_fail(c->rank, "pf_set_arithmetic: flavour %d (%d PF_ARITH_FAST, %d PF_ARITH_EXACT)", flavour, PF_ARITH_FAST, PF_ARITH_EXACT);
+  arithmetic_set(c, flavour == PF_ARITH_FAST);
+  return 0;
+}
+extern "C" int pf_get_arithmetic(pf_ctx *c) { return c ? (c->fast_libm ? PF_ARITH_FAST : PF_ARITH_EXACT) : -1; }
+
+extern "C" int pf_flavour_census(pf_ctx *c, int ns, const double *radius_cells, double *true_variance, pf_census *out, size_t capacity, pf_census_cell *cells) {
+  const char *who = "pf_flavour_census";
+  if (!c || !radius_cells || !out || (capacity && !cells)) return pf_fail(c ? c->rank : 0, "%s: null argument", who);
+  if (ns < 1 || ns > PF_MAX_SMOOTH) return pf_fail(c->rank, "%s: Nsmooth %d not in [1, %d]", who, ns, PF_MAX_SMOOTH);
+  if (!c->have_density) return pf_fail(c->rank, "%s: density not set", who);
+  const size_t nc = ncell(c);
+  // the shadow columns live for this call alone and are not the context's (pf_device_bytes does not count them)
+  struct Shadow { void *f; int *r; ~Shadow() { hipFree(f); hipFree(r); } } sh = {nullptr, nullptr};
+  if (hipMalloc(&sh.f, nc * (size_t)c->pb) != hipSuccess || hipMalloc((void **)&sh.r, nc * sizeof(int)) != hipSuccess) {
+    (void)hipGetLastError();
+    return pf_fail(c->rank, "%s: cannot allocate the %zu bytes of the shadow Fmax / Rmax columns on the device (%.1f GB held by this context)", who,
+                   nc * ((size_t)c->pb + sizeof(int)), 1e-9 * c->dev_bytes);
+  }
+  const bool own_fast = c->fast_libm;
+  arithmetic_set(c, !own_fast);
+  int rc = pf_sweep(c, ns, radius_cells, true_variance);
+  arithmetic_set(c, own_fast);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(sh.f, c->fmax, nc * (size_t)c->pb, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(sh.r, c->rmax, nc * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+  rc = pf_sweep(c, ns, radius_cells, true_variance);
+  if (rc) return rc;
+  const void *ff = own_fast ? c->fmax : sh.f, *fe = own_fast ? sh.f : c->fmax;
+  const int *rf = own_fast ? c->rmax : sh.r, *re = own_fast ? sh.r : c->rmax;
+  KTimer t(c, KS_MISC, (double)nc * (2.0 * c->pb + 8.0));
+  return pf_census_device(who, c->rank, c->pb, 0, nc, ff, rf, fe, re, out, capacity, cells, c->stream);
 }
 extern "C" int pf_debug_invariant_reruns(pf_ctx *c) { return c ? c->inv_reruns : -1; }
 extern "C" int pf_solve_ran_beside_zpass(pf_ctx *c) { return c ? (c->solve_ran_beside ? 1 : 0) : -1; }

@@ -369,6 +369,10 @@ void pf_plc_release(void *state);
 // ---- pf_catalog.hip: the halo catalogue and the mass function of an output; it reads the tables the light-cone state keeps ----
 struct PfPlcTab;
 bool pf_plc_tables(pf_ctx *c, PfPlcTab *tab, int *tab_doubles);   // false: no cosmology set
+// ---- pf_census.hip: the census of the Fmax / Rmax columns of the two flavours of the solve (pf_flavour_census in pf_api.hip runs the sweeps) ----
+// four columns of `count` cells on the device (pb bytes per Fmax) -> *out and the first min(outliers, capacity) records, both on the host
+int pf_census_device(const char *who, int task, int pb, unsigned long long first_cell, size_t count, const void *fmax_fast, const int *rmax_fast,
+                     const void *fmax_exact, const int *rmax_exact, pf_census *out, size_t capacity, pf_census_cell *cells, hipStream_t st);
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);
