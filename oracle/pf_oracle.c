@@ -1155,6 +1155,11 @@ int orc_set_growth_table(orc_ctx *c, int order, const double *T, int nk, double 
 int orc_set_growth(orc_ctx *c, const double g[4]) { memcpy(c->growth, g, sizeof(double) * 4); return 0; }
 const orc_product *orc_products(orc_ctx *c) { return c->products; }
 const double *orc_second_derivative(orc_ctx *c, int i) { return c->second_derivatives[i]; }
+int orc_set_second_derivative(orc_ctx *c, int i, const double *field) {
+  if (!c || !field || i < 0 || i > 5 || !c->second_derivatives[i]) return 1;
+  par_copy(c, c->second_derivatives[i], field, c->n_r);
+  return 0;
+}
 const double *orc_kvector(orc_ctx *c, int which) {
   return which == 0 ? c->kvector_2LPT : which == 1 ? c->kvector_3LPT_1 : c->kvector_3LPT_2;
 }

@@ -86,6 +86,8 @@ int orc_fmax_pdf(orc_ctx *c, unsigned long long hist[ORC_NBINS]); /* fmax.c:509 
 /* accessors */
 const orc_product *orc_products(orc_ctx *c);
 const double *orc_second_derivative(orc_ctx *c, int i); /* i=0..5, order 11,22,33,12,13,23 */
+/* a caller's [n][n][n] field in place of second derivative i: the collapse pass that follows solves on it (equal-input tests) */
+int orc_set_second_derivative(orc_ctx *c, int i, const double *field);
 const double *orc_kvector(orc_ctx *c, int which);       /* 0:2LPT 1:3LPT_1 2:3LPT_2 */
 
 /* stand-alone FFTs on caller buffers (for unit tests of the oracle itself) */

@@ -83,6 +83,7 @@ def lib(double_products: bool = False):
         L.orc_products.argtypes = [C.c_void_p]
         L.orc_second_derivative.restype = dp
         L.orc_second_derivative.argtypes = [C.c_void_p, C.c_int]
+        L.orc_set_second_derivative.argtypes = [C.c_void_p, C.c_int, dp]
         L.orc_kvector.restype = dp
         L.orc_kvector.argtypes = [C.c_void_p, C.c_int]
         L.orc_c2r.argtypes = [C.c_void_p, dp, dp]
@@ -196,6 +197,16 @@ class Oracle:
         n = self.n
         return [np.ctypeslib.as_array(self.L.orc_second_derivative(self.h, i), shape=(n, n, n)).copy()
                 for i in range(6)]
+
+    def set_second_derivatives(self, H):
+        """six [n][n][n] fields (order 11, 22, 33, 12, 13, 23) in place of the context's own second derivatives: the
+        collapse_times(ismooth) that follows runs the whole compute_collapse_times on them (the collapse pass on equal input)"""
+        n = self.n
+        assert len(H) == 6
+        for i, h in enumerate(H):
+            h = np.ascontiguousarray(h, dtype=np.float64)
+            assert h.shape == (n, n, n), h.shape
+            assert self.L.orc_set_second_derivative(self.h, i, _dp(h)) == 0
 
     def collapse_times(self, ismooth: int) -> float:
         tv = C.c_double(0)
