@@ -866,6 +866,16 @@ int pf_debug_gfft_lines(int n, int mode, int dir, int nlines, const double *in, 
    along the transformed axis into out[j] ([njobs][nouter][n][ncols]); jobs on the same input must be adjacent.  n a power of two. */
 int pf_debug_strided_jobs(int field_bytes, int n, int njobs, int nin, const int *in_of, const int *mul, int nouter, int ncols,
                           const double *in, double *out);
+/* ... and the same launch the way the passes of a pruned (band-limited) radius issue it: loads with |wavenumber| > band_e along the
+   transformed axis are zeros, outer lines with |signed index of (outer + outer_offset)| > band_outer leave early (a band >= n / 2
+   switches either off), pre / rs / growth are the first-pass filter of pf_debug_lines, and the device rows of the inputs / outputs are
+   in_pitch / out_pitch complex columns long (each whole 128-byte lines -- a multiple of 8 with fp64, of 16 with fp32 fields -- and
+   >= ncols; they may differ: the x-pass of a pruned radius writes the compact pitch of its band).  The input rows' padding beyond ncols holds junk, not zeros.  Behind every output field lies a
+   guard region filled with a fixed byte pattern: *guard_ok = 1 when all of them came back intact.  in: [nin][nouter][n][ncols],
+   out: [njobs][nouter][n][ncols] (the columns below ncols of the device rows); lines that left early come back as zeros. */
+int pf_debug_strided_band(int field_bytes, int n, int njobs, int nin, const int *in_of, const int *mul, int nouter, int ncols,
+                          int in_pitch, int out_pitch, int band_e, int band_outer, int outer_offset, int pre, double rs, double growth,
+                          const double *in, double *out, int *guard_ok);
 /* how many sweeps of this context were repeated with six components per cell because the invariant z-pass met a tensor
    with q == 0 that is not exactly isotropic (the reference's "already diagonal" branch, src/collapse_times.c:722-727) */
 int pf_debug_invariant_reruns(pf_ctx *ctx);

@@ -2933,6 +2933,84 @@ extern "C" int pf_debug_strided_jobs(int field_bytes, int n, int njobs, int nin,
   return rc;
 }
 
+// ... and that launch as the passes of a pruned radius issue it (xpass / ypass above with band < n / 2): band_e, band_outer, the first-pass
+// filter, and device rows of in_pitch / out_pitch complex columns -- the output may carry the compact pitch band_zpitch gives while the
+// input keeps the full one.  The padding of the input rows (columns ncols .. in_pitch) holds junk (bytes 0x7f: finite, huge), which no
+// output column below ncols may depend on.  Every output field lies in a slot of its own, long enough for a kernel that took the
+// input's pitch for the output's: what follows the field in its slot is the guard region (bytes 0xa5), and *guard_ok says whether all
+// of them came back as they were.  in: [nin][nouter][n][ncols]; out: [njobs][nouter][n][ncols], zeros where nothing was stored.
+extern "C" int pf_debug_strided_band(int field_bytes, int n, int njobs, int nin, const int *in_of, const int *mul, int nouter, int ncols,
+                                     int in_pitch, int out_pitch, int band_e, int band_outer, int outer_offset, int pre, double rs, double growth,
+                                     const double *in, double *out, int *guard_ok) {
+  if (!in || !out || !in_of || !mul || !guard_ok || njobs < 1 || njobs > PF_MAX_JOBS || nin < 1 || nin > njobs || nouter < 1 || ncols < 1 ||
+      (field_bytes != 8 && field_bytes != 4) || n < 16 || n > 2048 || ((n & (n - 1)) && !pf_mixed_supported(n)) || band_e < 0 || band_outer < 0 ||
+      outer_offset < 0 || outer_offset >= n)
+    return pf_fail(0, "pf_debug_strided_band: bad argument");
+  const int fb = field_bytes, line = 64 / fb;  // complex numbers per 128-byte line
+  if (in_pitch < ncols || out_pitch < ncols || in_pitch % line || out_pitch % line || in_pitch > 4096 || out_pitch > 4096)
+    return pf_fail(0, "pf_debug_strided_band: rows of %d columns need pitches of whole 128-byte lines (%d complex) that hold them, not %d / %d", ncols, line, in_pitch, out_pitch);
+  for (int j = 0; j < njobs; j++) if (in_of[j] < 0 || in_of[j] >= nin) return pf_fail(0, "pf_debug_strided_band: in_of");
+  *guard_ok = 0;
+  pf_ctx *nc = nullptr;
+  const size_t nrows = (size_t)nouter * n, cb = (size_t)2 * fb;                       // bytes of a complex number
+  const size_t in_field = nrows * (size_t)in_pitch * cb, out_field = nrows * (size_t)out_pitch * cb;
+  const size_t slot = (in_field > out_field ? in_field : out_field) + 4096, guard = slot - out_field;
+  void *d_in = nullptr, *d_out = nullptr, *d_tw = nullptr; double *d_etab = nullptr;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return pf_fail(0, "pf_debug_strided_band: no HIP device");
+  std::vector<char> tw;
+  host_twiddles(n, fb, tw);
+  auto body = [&]() -> int {
+    HIPCHK(nc, hipMalloc(&d_in, (size_t)nin * in_field));
+    HIPCHK(nc, hipMalloc(&d_out, (size_t)njobs * slot));
+    HIPCHK(nc, hipMalloc(&d_tw, tw.size()));
+    HIPCHK(nc, hipMalloc((void **)&d_etab, (size_t)n * sizeof(double)));
+    HIPCHK(nc, hipMemcpy(d_tw, tw.data(), tw.size(), hipMemcpyHostToDevice));
+    HIPCHK(nc, hipMemset(d_in, 0x7f, (size_t)nin * in_field));
+    for (int j = 0; j < njobs; j++) {
+      HIPCHK(nc, hipMemset((char *)d_out + (size_t)j * slot, 0, out_field));
+      HIPCHK(nc, hipMemset((char *)d_out + (size_t)j * slot + out_field, 0xa5, guard));
+    }
+    const size_t hrow = (size_t)ncols * cb, hfield = nrows * (size_t)ncols * 2;
+    std::vector<float> hf;
+    for (int i = 0; i < nin; i++) {
+      const void *src = in + (size_t)i * hfield;
+      if (fb == 4) { hf.resize(hfield); for (size_t k = 0; k < hfield; k++) hf[k] = (float)in[(size_t)i * hfield + k]; src = hf.data(); }
+      HIPCHK(nc, hipMemcpy2D((char *)d_in + (size_t)i * in_field, (size_t)in_pitch * cb, src, hrow, hrow, nrows, hipMemcpyHostToDevice));
+    }
+    PfStridedParams p; memset(&p, 0, sizeof(p));
+    p.njobs = njobs;
+    for (int j = 0; j < njobs; j++) { p.job[j].in = (char *)d_in + (size_t)in_of[j] * in_field; p.job[j].out = (char *)d_out + (size_t)j * slot; p.job[j].mul = mul[j]; }
+    p.ain.os = (long long)n * in_pitch; p.ain.el_shift = (n & (n - 1)) ? 0 : ilog2i(n); p.ain.el_len = n; p.ain.ehs = 0; p.ain.els = in_pitch;
+    p.aout = p.ain; p.aout.os = (long long)n * out_pitch; p.aout.els = out_pitch;
+    p.ncols = ncols; p.nouter = nouter; p.pre = pre ? 1 : 0; p.outer_offset = outer_offset; p.rs = rs; p.growth = growth; p.tw = d_tw; p.etab = d_etab; p.dev = dev;
+    p.band_e = band_e < n / 2 ? band_e : n; p.band_outer = band_outer < n / 2 ? band_outer : n;
+    if (pre && rs != 0.0) PFCHK0(pf_launch_exp_table(d_etab, n, rs, nullptr));
+    PFCHK0(pf_launch_strided(fb, n, +1, p, nullptr));
+    HIPCHK(nc, hipDeviceSynchronize());
+    for (int j = 0; j < njobs; j++) {
+      const char *f = (const char *)d_out + (size_t)j * slot;
+      if (fb == 8) HIPCHK(nc, hipMemcpy2D(out + (size_t)j * hfield, hrow, f, (size_t)out_pitch * cb, hrow, nrows, hipMemcpyDeviceToHost));
+      else {
+        hf.resize(hfield);
+        HIPCHK(nc, hipMemcpy2D(hf.data(), hrow, f, (size_t)out_pitch * cb, hrow, nrows, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < hfield; k++) out[(size_t)j * hfield + k] = (double)hf[k];
+      }
+    }
+    std::vector<unsigned char> g(guard);
+    int ok = 1;
+    for (int j = 0; j < njobs; j++) {
+      HIPCHK(nc, hipMemcpy(g.data(), (const char *)d_out + (size_t)j * slot + out_field, guard, hipMemcpyDeviceToHost));
+      for (size_t k = 0; k < guard; k++) if (g[k] != 0xa5) { ok = 0; break; }
+    }
+    *guard_ok = ok;
+    return 0;
+  };
+  const int rc = body();
+  hipFree(d_in); hipFree(d_out); hipFree(d_tw); hipFree(d_etab);
+  return rc;
+}
+
 // used by pf_rccl.cpp
 extern "C" int pf_ctx_set_rccl(pf_ctx *c, void *link) {
   if (!c) return 1;

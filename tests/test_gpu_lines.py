@@ -2,11 +2,16 @@
 the strided x/y pass (k_strided), the z-pass c2r (k_c2r / k_c2r_persistent), the forward z-pass (k_r2c) and the six-row
 invariant z-pass (k_c2r_invariants), fp64 and fp32 fields, with and without band pruning and with the k-space factors of
 compute_derivative (src/fmax-pfft.c:306-397).  N = 2048 is the row length of BASELINE config 5 (2048^3 on eight GPUs): its
-box does not fit one GPU, its kernels do -- pf_debug_lines runs them on a batch of lines without a context."""
+box does not fit one GPU, its kernels do -- pf_debug_lines runs them on a batch of lines without a context.
+The band-limited (pruned) forms of the passes are held to the same reference at every band of a ladder that sits on the edges each
+kernel family cuts a band by (tests/band_ladder.py: which granule belongs to which kernel, with file:line), and the strided launch of a
+pruned radius -- several jobs, ncols = band + 1, the compact output pitch, outer lines beyond the band -- through pf_debug_strided_band."""
 import ctypes as C
 
 import numpy as np
 import pytest
+
+import band_ladder as B
 
 pytestmark = pytest.mark.gpu
 
@@ -38,11 +43,11 @@ def run(L, fb, n, pas, inp, out_shape, mul=0, band=1 << 30, nouter=1, ncols=1, p
     return out
 
 
-def run_invariants(L, n, x, rows, fb=8):
+def run_invariants(L, n, x, rows, fb=8, band=1 << 30):
     """pass 4: six spectra rows -> (mu1, mu2, mu3) rows (fp64 whatever the fields are), plus the q == 0 flag"""
     x = np.ascontiguousarray(x)
     out = np.zeros(3 * rows * n + 1)
-    rc = L.pf_debug_lines(fb, n, 4, 0, 1 << 30, rows, 1, 0, 0.0, 1.0, 0, _dp(x.view(np.float64)), _dp(out))
+    rc = L.pf_debug_lines(fb, n, 4, 0, band, rows, 1, 0, 0.0, 1.0, 0, _dp(x.view(np.float64)), _dp(out))
     assert rc == 0, L.pf_last_error()
     return out[:-1].reshape(3, rows, n), out[-1]
 
@@ -275,3 +280,228 @@ def test_strided_launch_with_several_jobs_per_tile(L, n, fb):
     for j in range(6):
         want = np.fft.ifft(x[in_of[j]] * kfactor(int(mul[j]), k)[None, :, None], axis=1) * n
         assert np.max(np.abs(out[j] - want)) <= tol(fb, n) * np.max(np.abs(want)), (n, fb, j)
+
+
+# ---- band-limited (pruned) passes at the edges of the band: tests/band_ladder.py ----
+# Which kernel a size selects:
+#   pf_launch_strided (csrc/pf_fft_kernels.hip:1114-1137): a power of two with fp64 fields -> k_strided<double, N> (launch_strided_n, :992-1006;
+#     128 and 1024 with the paired radix-16 first stage, :106; 2048 in tiles of four columns, :963); fp32 fields -> launch_strided_f32
+#     (:1013-1020): 1024 -> k_strided_pk8 and 2048 -> k_strided16 (pf_launch_strided16, csrc/pf_fft16_kernels.hip:414-446), below that
+#     k_strided<float, N>; any other size -> pf_launch_mixed_strided (csrc/pf_mixed_kernels.hip:843-898): 24 and 40 with a run-time
+#     plan, from 96 on (96, 200, 768, 1000) with the plan compiled in (:745-747)
+#   pf_launch_c2r (csrc/pf_fft_kernels.hip:1157-1168; launch_c2r_n, :1029-1049): k_c2r_persistent, k_c2r with PF_ZPASS_PERSIST=0 and for
+#     16 points always (:1040); other sizes -> pf_launch_mixed_c2r (csrc/pf_mixed_kernels.hip:901-928)
+#   pf_launch_c2r_invariants (csrc/pf_fft_kernels.hip:1183-1197; launch_c2r_invariants_n, :1052-1087): fp32 rows of 512 and 1024 points ->
+#     k_c2r_invariants_pk2 (:1068), rows with reducing waves (1024 fp64, 512, 2048 fp32: PfZiPlan::spec0, :474-476) ->
+#     k_c2r_invariants_spec, else k_c2r_invariants; other sizes -> pf_launch_mixed_c2r_invariants (csrc/pf_mixed_kernels.hip:967-)
+INV_SIZES = [n for n in B.LADDER_SIZES if n != 2048]   # pf_c2r_invariants_supported: fp64 rows up to 1024 points, fp32 up to 2048
+
+
+@pytest.mark.parametrize("n", B.LADDER_SIZES)
+@pytest.mark.parametrize("fb", [8, 4])
+def test_strided_pass_band_ladder(L, n, fb):
+    """pass 0 at every band of the ladder: loads beyond the band are exact zeros of the input, nothing inside it is lost.  mul = 2 is even
+    in k, mul = 3 (i k) odd: a slip of sign or of one element on the negative half of the band shows in the second"""
+    rng = np.random.default_rng(17 * n + fb)
+    nouter, ncols = 3, 21
+    x = rng.standard_normal((nouter, n, ncols)) + 1j * rng.standard_normal((nouter, n, ncols))
+    k = 2 * np.pi / n * signed(n)
+    s = np.abs(signed(n))
+    for mul in (2, 3):
+        xk = x * kfactor(mul, k)[None, :, None]
+        full = run(L, fb, n, 0, x, x.shape, mul=mul, nouter=nouter, ncols=ncols)
+        for band in B.band_ladder(n, fb):
+            got = run(L, fb, n, 0, x, x.shape, mul=mul, band=band, nouter=nouter, ncols=ncols)
+            want = np.fft.ifft(xk * (s <= band)[None, :, None], axis=1) * n
+            assert np.max(np.abs(got - want)) <= tol(fb, n) * np.max(np.abs(want)), (n, fb, mul, band)
+            if band == n // 2:
+                assert np.array_equal(got, full), (n, fb, mul, "band n/2 is no band")
+
+
+@pytest.mark.parametrize("n", B.LADDER_SIZES)
+@pytest.mark.parametrize("fb", [8, 4])
+def test_first_pass_filter_with_a_band_on_lines(L, n, fb):
+    """the x-pass of a pruned radius: the first-pass filter (pre = 1) AND band-limited loads, outer rows n-2, n-1, 0, 1"""
+    rng = np.random.default_rng(19 * n + fb)
+    nouter, ncols, off = 4, 9, n - 2
+    x = rng.standard_normal((nouter, n, ncols)) + 1j * rng.standard_normal((nouter, n, ncols))
+    ke = 2 * np.pi / n * signed(n)
+    s = np.abs(signed(n))
+    so = (np.arange(nouter) + off)
+    so = np.where(so > n // 2, so - n, so).astype(np.float64)
+    ko = 2 * np.pi / n * so
+    kc = 2 * np.pi / n * np.arange(ncols)
+    k2 = ko[:, None, None] ** 2 + ke[None, :, None] ** 2 + kc[None, None, :] ** 2
+    for rs, g, mul in ((0.0, 1.0, 0), (2.5, 0.37, 2), (0.0, -0.111, 3)):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            f = np.where(k2 > 0, np.exp(-0.5 * k2 * rs * rs) * g / k2, 0.0)
+        xf = x * f * kfactor(mul, ke)[None, :, None]
+        for band in B.band_ladder(n, fb):
+            got = run(L, fb, n, 0, x, x.shape, mul=mul, band=band, nouter=nouter, ncols=ncols, pre=1, rs=rs, growth=g, outer_offset=off)
+            want = np.fft.ifft(xf * (s <= band)[None, :, None], axis=1) * n
+            assert np.max(np.abs(got - want)) <= 4 * tol(fb, n) * np.max(np.abs(want)), (n, fb, rs, mul, band)
+
+
+@pytest.mark.parametrize("n", B.LADDER_SIZES)
+@pytest.mark.parametrize("fb", [8, 4])
+@pytest.mark.parametrize("persist", ["24", "0"])
+def test_zpass_c2r_band_ladder(L, n, fb, persist, monkeypatch):
+    """pass 2 at every band of the ladder (columns kz > band are not read), an odd number of rows"""
+    monkeypatch.setenv("PF_ZPASS_PERSIST", persist)
+    rng = np.random.default_rng(23 * n + fb)
+    rows, h = 37, n // 2 + 1
+    x = rng.standard_normal((rows, h)) + 1j * rng.standard_normal((rows, h))
+    kz = 2 * np.pi / n * np.arange(h)
+    for mul in (1, 2):
+        xk = x * kfactor(mul, kz)[None, :]
+        for band in B.band_ladder(n, fb):
+            got = run(L, fb, n, 2, x, (rows, n), mul=mul, band=band, nouter=rows)
+            want = np.fft.irfft(xk * (np.arange(h) <= band), n=n, axis=1) * n
+            assert np.max(np.abs(got - want)) <= tol(fb, n) * np.max(np.abs(want)), (n, fb, mul, band)
+
+
+@pytest.mark.parametrize("n,fb", [(n, 8) for n in INV_SIZES] + [(n, 4) for n in B.LADDER_SIZES])
+def test_invariant_zpass_band_ladder(L, n, fb):
+    """pass 4 -- the z-pass of every sweep radius but the last -- at every band of the ladder; an odd number of rows (the fp32 form of
+    512 and 1024 points takes them in pairs).  The invariants are those of the six band-limited rows"""
+    rng = np.random.default_rng(29 * n + fb)
+    rows, h = (23 if fb == 8 else 11), n // 2 + 1
+    x = rng.standard_normal((6, rows, h)) + 1j * rng.standard_normal((6, rows, h))
+    if fb == 4:
+        x = x.astype(np.complex64).astype(np.complex128)
+    kz = 2 * np.pi / n * np.arange(h)
+    mul6 = (0, 0, 2, 0, 1, 1)
+    xk = [x[j] * kfactor(mul6[j], kz)[None, :] for j in range(6)]
+    for band in B.band_ladder(n, fb):
+        inb = np.arange(h) <= band
+        d = [np.fft.irfft(xk[j] * inb, n=n, axis=1) * n for j in range(6)]
+        got, flag = run_invariants(L, n, x, rows, fb=fb, band=band)
+        assert flag == 0.0
+        mu1 = d[0] + d[1] + d[2]
+        mu2 = 0.5 * mu1 * mu1 - 0.5 * (d[0] ** 2 + d[1] ** 2 + d[2] ** 2) - (d[3] ** 2 + d[4] ** 2 + d[5] ** 2)
+        mu3 = d[0] * d[1] * d[2] + 2 * d[3] * d[4] * d[5] - d[0] * d[5] ** 2 - d[1] * d[4] ** 2 - d[2] * d[3] ** 2
+        amp = max(np.max(np.abs(v)) for v in d)
+        for gi, wi, p in ((got[0], mu1, 1), (got[1], mu2, 2), (got[2], mu3, 3)):
+            assert np.max(np.abs(gi - wi)) <= 8 * tol(fb, n) * amp ** p, (n, fb, band, p)
+
+
+# ---- the strided launch as the passes of a pruned radius issue it: pf_debug_strided_band ----
+def run_band(L, fb, n, x, in_of, mul, ncols, in_pitch, out_pitch, band_e=1 << 30, band_outer=1 << 30, outer_offset=0, pre=0, rs=0.0, growth=1.0):
+    """x: [nin][nouter][n][ncols] -> ([njobs][nouter][n][ncols], guard regions intact)"""
+    x = np.ascontiguousarray(x)
+    nin, nouter = x.shape[0], x.shape[1]
+    assert x.shape[2:] == (n, ncols)
+    in_of = np.asarray(in_of, dtype=np.int32)
+    mul = np.asarray(mul, dtype=np.int32)
+    out = np.zeros((len(mul), nouter, n, ncols), dtype=np.complex128)
+    ok = C.c_int(-1)
+    ip = C.POINTER(C.c_int)
+    rc = L.pf_debug_strided_band(fb, n, len(mul), nin, in_of.ctypes.data_as(ip), mul.ctypes.data_as(ip), nouter, ncols, in_pitch, out_pitch,
+                                 band_e, band_outer, outer_offset, pre, rs, growth, _dp(x.view(np.float64)), _dp(out.view(np.float64)), C.byref(ok))
+    assert rc == 0, L.pf_last_error()
+    return out, ok.value
+
+
+def up(v, m):
+    return (v + m - 1) // m * m
+
+
+def signed_outer(n, nouter, off):
+    so = (np.arange(nouter) + off) % n
+    return np.where(so > n // 2, so - n, so)
+
+
+BAND_TAP_SIZES = [(2048, 4), (1024, 4), (1024, 8), (256, 4), (768, 8), (200, 4), (40, 8)]
+
+
+@pytest.mark.parametrize("n,fb", BAND_TAP_SIZES)
+def test_band_limited_launch_with_several_jobs_per_tile(L, n, fb):
+    """the six-job, three-input launch of the sweep's y-pass with band-limited loads: a tile kept in registers over its jobs (k_strided,
+    k_strided_pk8, k_mixed_strided with a compile-time plan) is masked once, a tile read again per job (k_strided16, k_mixed_strided with
+    a run-time plan) by every job -- at band 1, at every granule edge of the ladder and at n/2 - 1"""
+    rng = np.random.default_rng(31 * n + fb)
+    nouter, ncols, nin = 2, 37, 3
+    x = rng.standard_normal((nin, nouter, n, ncols)) + 1j * rng.standard_normal((nin, nouter, n, ncols))
+    in_of = [0, 1, 1, 2, 2, 2]
+    mul = [0, 1, 0, 2, 1, 3]
+    k = 2 * np.pi / n * signed(n)
+    s = np.abs(signed(n))
+    xk = [x[in_of[j]] * kfactor(mul[j], k)[None, :, None] for j in range(6)]
+    req = B.required(n, fb)
+    bands = sorted({1, n // 2 - 1} | {b for name, v in req.items() if name.startswith("g") for b in v})
+    pitch = up(ncols, 16)
+    for band in bands:
+        got, ok = run_band(L, fb, n, x, in_of, mul, ncols, pitch, pitch, band_e=band)
+        assert ok == 1, (n, fb, band, "guard")
+        for j in range(6):
+            want = np.fft.ifft(xk[j] * (s <= band)[None, :, None], axis=1) * n
+            assert np.max(np.abs(got[j] - want)) <= tol(fb, n) * np.max(np.abs(want)), (n, fb, band, j)
+
+
+PRUNED_X_SIZES = BAND_TAP_SIZES + [(2048, 8), (128, 8), (96, 4)]
+
+
+def pruned_x_reference(n, x, nouter, off, ncols, rs, g, band):
+    """the Hessian x-pass (1 -> 3: one, k, k^2 with the first-pass filter) of the in-band part of x, by pocketfft"""
+    ke = 2 * np.pi / n * signed(n)
+    ko = 2 * np.pi / n * signed_outer(n, nouter, off).astype(np.float64)
+    kc = 2 * np.pi / n * np.arange(ncols)
+    k2 = ko[:, None, None] ** 2 + ke[None, :, None] ** 2 + kc[None, None, :] ** 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f = np.where(k2 > 0, np.exp(-0.5 * k2 * rs * rs) * g / k2, 0.0)
+    xf = x * f * (np.abs(signed(n)) <= band)[None, :, None]
+    return [np.fft.ifft(xf * kfactor(m, ke)[None, :, None], axis=1) * n for m in (0, 1, 2)]
+
+
+@pytest.mark.parametrize("n,fb", PRUNED_X_SIZES)
+def test_pruned_x_pass_writes_the_compact_pitch(L, n, fb):
+    """the x-pass of a pruned radius as xpass() launches it (csrc/pf_api.hip:831-861): ncols = band + 1, band_e = band_outer = band, the
+    first-pass filter, input rows of the full pitch and output rows of the compact pitch band_zpitch gives -- at bands whose band + 1 is
+    one below, exactly, and one above a whole number of 128-byte lines (the pitch then has one, no, and all but one column of padding).
+    Every in-band column of every in-band outer line is held against pocketfft; the rows' padding is not looked at; nothing may be
+    written behind a field"""
+    rng = np.random.default_rng(37 * n + fb)
+    m = B.line_granule(fb)
+    nzp = up(n // 2 + 1, 16)                                     # the full row pitch of the input
+    nouter, off, rs, g = 4, n - 2, 0.5, 0.37                      # outer lines -2, -1, 0, 1; a window that leaves every mode visible
+    lines = [k * m for k in (1, 2)] + [q for q in (128,) if m < q < n // 2]
+    bands = sorted({b for q in lines for b in (q - 2, q - 1, q) if 1 <= b < n // 2})
+    for band in bands:
+        ncols = band + 1
+        zp = B.band_zpitch(n, fb, band, nzp)
+        assert zp % m == 0 and ncols <= zp < ncols + m
+        x = rng.standard_normal((1, nouter, n, ncols)) + 1j * rng.standard_normal((1, nouter, n, ncols))
+        got, ok = run_band(L, fb, n, x, [0, 0, 0], [0, 1, 2], ncols, nzp, zp, band_e=band, band_outer=band, outer_offset=off, pre=1, rs=rs, growth=g)
+        assert ok == 1, (n, fb, band, "guard")
+        want = pruned_x_reference(n, x[0], nouter, off, ncols, rs, g, band)
+        inb = np.abs(signed_outer(n, nouter, off)) <= band
+        assert inb.any()
+        for j in range(3):
+            assert np.max(np.abs(got[j][inb] - want[j][inb])) <= 4 * tol(fb, n) * np.max(np.abs(want[j][inb])), (n, fb, band, j)
+
+
+@pytest.mark.parametrize("n,fb", PRUNED_X_SIZES)
+def test_outer_lines_beyond_the_band_leave_early(L, n, fb):
+    """band_outer: outer lines on both sides of +band, of -band and of the Nyquist line.  Every line with |signed outer index| <= band
+    is held against pocketfft (its filter carries the line's own wavenumber); the lines beyond are never read by the passes that
+    follow and are not compared -- but they may not write behind a field either"""
+    rng = np.random.default_rng(41 * n + fb)
+    m = B.line_granule(fb)
+    nouter, ncols, rs, g = 4, 21, 0.5, -0.111
+    pitch = up(ncols, 16)
+    x = rng.standard_normal((1, nouter, n, ncols)) + 1j * rng.standard_normal((1, nouter, n, ncols))
+    bands = sorted({b for b in (1, 2, m - 1, m, 64, n // 2 - 2, n // 2 - 1) if 1 <= b < n // 2})
+    compared = 0
+    for band in bands:
+        for off in (band - 1, n - band - 2, n // 2 - 1):          # band-1 .. band+2;  -band-2 .. -band+1;  n/2-1, n/2, -n/2+1, -n/2+2
+            so = signed_outer(n, nouter, off)
+            inb = np.abs(so) <= band
+            got, ok = run_band(L, fb, n, x, [0, 0, 0], [0, 1, 2], ncols, pitch, pitch, band_e=band, band_outer=band, outer_offset=off, pre=1, rs=rs, growth=g)
+            assert ok == 1, (n, fb, band, off, "guard")
+            if not inb.any():
+                continue
+            want = pruned_x_reference(n, x[0], nouter, off, ncols, rs, g, band)
+            for j in range(3):
+                assert np.max(np.abs(got[j][inb] - want[j][inb])) <= 4 * tol(fb, n) * np.max(np.abs(want[j][inb])), (n, fb, band, off, j)
+            compared += int(inb.sum())
+    assert compared >= 2 * len(bands)

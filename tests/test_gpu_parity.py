@@ -622,6 +622,65 @@ def test_pruned_transform_equals_full_transform(api, monkeypatch):
             assert np.max(np.abs(a - b)) <= 4e-16 * amp
 
 
+@pytest.mark.parametrize("n,fb,bands", [(128, 4, (15, 31, 63)), (96, 8, (7, 15, 47)), (40, 8, (7, 15, 19))])
+def test_pruned_transform_equals_full_transform_at_edge_bands(api, n, fb, bands, monkeypatch):
+    """... at the bands where the pruned passes change their shape: band + 1 a whole number of 128-byte lines (8 complex fp64, 16 fp32:
+    the compact row pitch of the x-pass output then has no padding at all) and n/2 - 1, the largest band hess_band returns -- with fp32
+    fields, with a mixed-radix plan compiled in (96) and with a run-time plan (40).  The radii are chosen from the restated hess_band
+    (tests/band_ladder.py).  fp64: the bound of the test above; fp32 fields: the Hessian contract of fp32 fields, rel-L2 <= 1e-5."""
+    import band_ladder as B
+    m = B.line_granule(fb)
+    assert any((b + 1) % m == 0 for b in bands) and n // 2 - 1 in bands
+    radii = [B.radius_of_band(n, b) for b in bands]
+    dk = synth.make_density(n, seed=101 + n)
+    out = {}
+    for eps in ("0", None):
+        if eps is None:
+            monkeypatch.delenv("PF_PRUNE_EPS", raising=False)
+        else:
+            monkeypatch.setenv("PF_PRUNE_EPS", eps)
+        with api.Fmax(n, field_bytes=fb) as f:
+            f.set_density(dk)
+            res = []
+            for rs in radii:
+                f.compute_second_derivatives(rs)
+                res.append([f.second_derivative(i) for i in range(6)])
+            out[eps] = res
+    for band, full, pruned in zip(bands, out["0"], out[None]):
+        amp = max(np.max(np.abs(h)) for h in full)
+        assert amp > 0
+        for i, (a, b) in enumerate(zip(full, pruned)):
+            if fb == 8:
+                assert np.max(np.abs(a - b)) <= 4e-16 * amp, (n, band, i)
+            else:
+                assert np.linalg.norm(a - b) <= 1e-5 * np.linalg.norm(a), (n, band, i)
+
+
+def test_pruned_sweep_equals_full_sweep_through_the_invariant_zpass(api, monkeypatch):
+    """a sweep whose first two radii are band-limited (bands 24 and 31 = n/2 - 1 at 64^3): their z-pass is the invariant one, which the
+    single-radius calls above never run.  TrueVariance of the pruned sweep against PF_PRUNE_EPS=0."""
+    import band_ladder as B
+    n = 64
+    radii = np.array([B.radius_of_band(n, 24), B.radius_of_band(n, 31), 0.0])
+    assert [B.hess_band(n, r) for r in radii[:2]] == [24, 31]
+    dk = synth.make_density(n, seed=77)
+    x, y = synth.invgrow_table("lcdm")
+    tv = {}
+    for eps in ("0", None):
+        if eps is None:
+            monkeypatch.delenv("PF_PRUNE_EPS", raising=False)
+        else:
+            monkeypatch.setenv("PF_PRUNE_EPS", eps)
+        with api.Fmax(n, timing=True) as f:
+            f.set_density(dk)
+            f.set_invgrow(x, y)
+            f.reset_kernel_stats()
+            tv[eps] = np.array(f.sweep(radii))
+            assert "zpass_c2r_hess_6to3inv" in {k["name"] for k in f.kernel_stats()}
+    assert np.all(tv["0"] > 0)
+    assert np.max(np.abs(tv[None] - tv["0"]) / tv["0"]) <= 1e-12
+
+
 def test_hmf_validation_run_on_gpu(api):
     """The reference's own committed validation run (HMF_Validation: 128^3, seed 486604, 9 radii) through the HIP
     path: same per-radius sigma (4 logged decimals), collapsed-cell count and Fmax histogram as the reference's
