@@ -952,6 +952,54 @@ int pf_debug_census(int product_bytes, unsigned long long first_cell, size_t cou
                     const void *fmax_fast, const int *rmax_fast, const void *fmax_exact, const int *rmax_exact,
                     pf_census *out, size_t capacity, pf_census_cell *cells);
 
+/* --- power spectrum and smoothed variances of a resident spectrum ---
+   What the reference plots as P(k) (tests/pk_and_HMF_tests) and logs per radius as "computed sigma" (src/fmax.c:142-146), from
+   the spectrum in HBM: two streaming reads of this rank's ky-slab, nothing else of size.
+   which: 0 the resident delta(k); 1, 2, 3 kvector_2LPT, kvector_3LPT_1, kvector_3LPT_2 -- the spectra pf_get_kvector(which - 1)
+     exports, refused under the same conditions as that export.
+   Wavenumbers: signed integers as in compute_derivative (src/fmax-pfft.c:312-334): i > n/2 -> i - n, n/2 stays positive;
+     k2 = ix^2 + iy^2 + iz^2, an integer.
+   Shell b of a mode: (2b - 1)^2 <= 4 k2 < (2b + 1)^2, the nearest integer to |k|, decided in integers (no tie: 4 k2 is even).
+     pf_power_bins(n) = 1 + the largest b with (2b - 1)^2 <= 3 n^2 (15 for n = 16); shell 0 holds only the k = 0 mode.
+   Weight w: 2 for 0 < iz < n/2, 1 on the planes iz = 0 and iz = n/2 -- the half-spectrum stands for the full sphere.
+   nmodes[b] = sum of w and k2sum[b] = sum of w k2 over ALL modes of the shell (exact integers; the nmodes add up to info->modes
+     = n^3 over all ranks).
+   power[b] = sum of w (re^2 + im^2) / N^6, N^6 = (n^3)^2, re and im widened to double first; P(k) of the shell is
+     power[b] / nmodes[b] * Box^3 at k_eff = (2 pi / Box) sqrt(k2sum[b] / nmodes[b]).
+   variance[i], i < ns = sum over k != 0 of w (re^2 + im^2) exp(-(2 pi / n)^2 k2 radius_cells[i]^2) / N^6: the window of
+     src/fmax-pfft.c:366-373 squared, so by Parseval the TrueVariance[i] that pf_sweep reports for that radius.  ns from 0 to
+     PF_MAX_SMOOTH; variance and radius_cells may be NULL when ns = 0.
+   info->nonfinite: the modes (counted with w) whose re^2 + im^2 is not finite -- a NaN or infinite part, or parts whose squares
+     overflow; they are in nmodes and k2sum and in no other sum.
+   Collective over the ranks exactly as pf_fmax_pdf is: every rank sums the rows of its own ky-slab (with a replicated delta(k)
+     too: its own n/P rows), the totals come through the installed pf_allreduce_fn (u64 and double) and every rank returns the
+     box's numbers.  Every transform path (pf_transform_path 0, 1, 2) is served.
+   The call reads the spectrum and changes nothing: products, flags, pf_device_bytes after the call and the arithmetic setting
+     are as before; its scratch is allocated for the call and freed before it returns.
+   No floating-point atomics: terms are added as fixed-point integers scaled to the largest term of their own shell (radius),
+     so the result is bitwise the same from run to run and for any launch geometry; what is dropped lies below 2^-95 of that
+     largest term.  The integer columns are identical for every rank count, the double ones differ between rank counts by rounding.
+   Refused (1, pf_last_error, nothing launched): null ctx / nmodes / k2sum / power / info, which outside 0..3, ns outside
+     [0, PF_MAX_SMOOTH], ns > 0 with a null radius_cells or variance, a radius that is negative or not finite, no density set
+     (which = 0), no resident source spectrum (which >= 1).
+   pf_debug_power_spectrum: test tap without a context, the production kernels on the rows y0 .. y0 + nyl - 1 of a caller's
+     spectrum -- a ky-slab [nyl][n (kx)][n/2+1][2] in fp64 on the host, converted to field_bytes on the way in; it returns that
+     slab's partial sums (the nmodes add up to info->modes = nyl n n).
+   pf_debug_power_times: with PF_POWER_TIMES=1 in the environment, ms[0] = device ms of the last call between events; 0 otherwise. */
+int pf_power_bins(int n);   /* number of shells for a grid of n points per side */
+typedef struct {
+  unsigned long long modes;      /* modes of this call's spectrum, full sphere: n^3 over all ranks */
+  unsigned long long nonfinite;  /* modes with a NaN or infinite part: counted here, in no sum */
+} pf_power_info;
+int pf_power_spectrum(pf_ctx *ctx, int which, int ns, const double *radius_cells,
+                      unsigned long long *nmodes, unsigned long long *k2sum, double *power,
+                      double *variance, pf_power_info *info);
+int pf_debug_power_spectrum(int field_bytes, int n, int y0, int nyl, const double *spec_host,
+                            int ns, const double *radius_cells,
+                            unsigned long long *nmodes, unsigned long long *k2sum, double *power,
+                            double *variance, pf_power_info *info);
+int pf_debug_power_times(double *ms);
+
 /* --- measurement --- */
 int pf_get_cputime(pf_ctx *ctx, pf_cputime *t);
 int pf_reset_cputime(pf_ctx *ctx);

@@ -131,6 +131,10 @@ class CensusCell(C.Structure):
     _fields_ = [("cell", C.c_ulonglong), ("fast", C.c_double), ("exact", C.c_double), ("rmax_fast", C.c_int), ("rmax_exact", C.c_int)]
 
 
+class PowerInfo(C.Structure):
+    _fields_ = [("modes", C.c_ulonglong), ("nonfinite", C.c_ulonglong)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -291,6 +295,11 @@ PROTOTYPES = {
     "pf_flavour_census": (C.c_int, [_vp, C.c_int, _dp, _dp, C.POINTER(Census), C.c_size_t, C.POINTER(CensusCell)]),
     "pf_debug_census": (C.c_int, [C.c_int, C.c_ulonglong, C.c_size_t, _vp, C.POINTER(C.c_int), _vp, C.POINTER(C.c_int), C.POINTER(Census), C.c_size_t,
                                   C.POINTER(CensusCell)]),
+    "pf_power_bins": (C.c_int, [C.c_int]),
+    "pf_power_spectrum": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _dp, _dp, C.POINTER(PowerInfo)]),
+    "pf_debug_power_spectrum": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _dp, _dp,
+                                          C.POINTER(PowerInfo)]),
+    "pf_debug_power_times": (C.c_int, [_dp]),
     "pf_get_cputime": (C.c_int, [_vp, C.POINTER(CpuTime)]),
     "pf_reset_cputime": (C.c_int, [_vp]),
     "pf_kernel_stats": (C.c_int, [_vp, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),

@@ -82,6 +82,50 @@ def point_times():
     return float(ms[0]), float(ms[1])
 
 
+def power_times():
+    """device ms of the last power_spectrum / debug_power_spectrum; zero without PF_POWER_TIMES=1 (pf_debug_power_times)"""
+    ms = (C.c_double * 1)()
+    _lib.load().pf_debug_power_times(ms)
+    return float(ms[0])
+
+
+def power_bins(n: int) -> int:
+    """shells of the power spectrum of a grid of n points per side (pf_power_bins)"""
+    return int(_lib.load().pf_power_bins(int(n)))
+
+
+_POWER_WHICH = {"density": 0, "kvector_2LPT": 1, "kvector_3LPT_1": 2, "kvector_3LPT_2": 3}
+
+
+def _power_call(L, n, radii_cells, call):
+    """the output arrays of a power call, `call(ns, radii, nmodes, k2sum, power, variance, info)` -> the dict of its results"""
+    r = np.ascontiguousarray(radii_cells, dtype=np.float64).reshape(-1)
+    nb = int(L.pf_power_bins(int(n)))
+    nm, k2 = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.uint64)
+    pw, var = np.zeros(nb), np.zeros(max(len(r), 1))
+    info = _lib.PowerInfo()
+    up = lambda a: a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    rc = call(len(r), dp(r) if len(r) else None, up(nm), up(k2), dp(pw), dp(var) if len(r) else None, C.byref(info))
+    return rc, {"nmodes": nm, "k2sum": k2, "power": pw, "variance": var[:len(r)].copy(), "modes": int(info.modes), "nonfinite": int(info.nonfinite)}
+
+
+def debug_power_spectrum(spec, y0: int = 0, field_bytes: int = 8, radii_cells=()):
+    """the power kernels on the rows y0 .. y0 + nyl - 1 of a caller's spectrum, a ky-slab [nyl][n (kx)][n/2+1] complex128
+    (pf_debug_power_spectrum) -> the dict of Fmax.power_spectrum with that slab's partial sums"""
+    L = _lib.load()
+    spec = np.ascontiguousarray(spec, dtype=np.complex128)
+    if spec.ndim != 3 or spec.shape[2] != spec.shape[1] // 2 + 1:
+        raise ValueError(f"a ky-slab [nyl][n][n/2+1], not {spec.shape}")
+    nyl, n = spec.shape[0], spec.shape[1]
+    sp = spec.view(np.float64).ctypes.data_as(C.POINTER(C.c_double))
+    rc, out = _power_call(L, n, radii_cells,
+                          lambda ns, r, nm, k2, pw, var, info: L.pf_debug_power_spectrum(int(field_bytes), n, int(y0), nyl, sp, ns, r, nm, k2, pw, var, info))
+    if rc:
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_power_spectrum failed")
+    return out
+
+
 _ARITH = {"fast": _lib.ARITH_FAST, "exact": _lib.ARITH_EXACT}
 # pf_census_cell: an outlier of the flavour census
 CENSUS_CELL_DTYPE = np.dtype([("cell", "<u8"), ("fast", "<f8"), ("exact", "<f8"), ("rmax_fast", "<i4"), ("rmax_exact", "<i4")], align=False)
@@ -1288,6 +1332,22 @@ class Fmax:
                                            rec.ctypes.data_as(C.POINTER(_lib.CensusCell)) if capacity else None))
         cen = _census_dict(out)
         return tv, cen, rec[:min(cen["outliers"], capacity)].copy()
+
+    def power_spectrum(self, which="density", radii_cells=(), box=None) -> dict:
+        """shell sums and Gaussian-smoothed variances of a spectrum that lies on the device (pf_power_spectrum; collective over the
+        ranks): which = "density" (0), "kvector_2LPT" (1), "kvector_3LPT_1" (2), "kvector_3LPT_2" (3) -> nmodes[], k2sum[], power[]
+        per shell, variance[] per radius (the TrueVariance a sweep reports for it), modes, nonfinite and, with the box length
+        `box`, k = (2 pi / box) sqrt(k2sum / nmodes) and pk = power / nmodes * box^3 per shell (NaN for an empty shell)"""
+        w = _POWER_WHICH.get(which, which)
+        rc, out = _power_call(self.L, self.n, radii_cells,
+                              lambda ns, r, nm, k2, pw, var, info: self.L.pf_power_spectrum(self.h, int(w), ns, r, nm, k2, pw, var, info))
+        self._chk(rc)
+        if box is not None:
+            nm = out["nmodes"].astype(np.float64)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                out["k"] = (2.0 * np.pi / float(box)) * np.sqrt(out["k2sum"].astype(np.float64) / nm)
+                out["pk"] = out["power"] / nm * float(box) ** 3
+        return out
 
     # -- measurement ------------------------------------------------------
     def cputime(self) -> dict:

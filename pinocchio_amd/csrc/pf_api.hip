@@ -2558,6 +2558,25 @@ extern "C" int pf_get_density(pf_ctx *c, double *host) {
   return export_spec(c, c->dk, host);
 }
 
+// what pf_power.hip sees of a context (pf_internal.h)
+void pf_ctx_spec_geometry(pf_ctx *c, PfSpecView *v) {
+  v->spec = nullptr; v->n = c->n; v->nzh = c->nzh; v->nzp = c->nzp; v->nyl = c->nyl; v->y0 = c->rank * c->nyl; v->fb = c->fb; v->rank = c->rank; v->P = c->P;
+  v->stream = c->stream;
+}
+int pf_ctx_spec_view(pf_ctx *c, const char *who, int which, PfSpecView *v) {
+  pf_ctx_spec_geometry(c, v);
+  if (which == 0) {
+    if (!c->have_density) return pf_fail(c->rank, "%s: density not set", who);
+    v->spec = c->dk;
+    return 0;
+  }
+  if (!c->have_sources) return pf_fail(c->rank, "%s: LPT sources not computed", who);
+  if (c->x_pending[which - 1]) PFCHK(c, finish_forward_x(c, which - 1));
+  v->spec = c->S[which - 1];
+  return 0;
+}
+int pf_ctx_allreduce(pf_ctx *c, void *buf_dev, size_t count, int is_u64) { return allreduce_dev(c, buf_dev, count, is_u64); }
+
 static int import_real(pf_ctx *c, const double *host, void *dst) {
   const long long nrows = (long long)c->nxl * c->n;
   if (handoff_h2d(c, staging(c), (const char *)host, (size_t)nrows * c->n * sizeof(double))) return 1;

@@ -373,6 +373,14 @@ bool pf_plc_tables(pf_ctx *c, PfPlcTab *tab, int *tab_doubles);   // false: no c
 // four columns of `count` cells on the device (pb bytes per Fmax) -> *out and the first min(outliers, capacity) records, both on the host
 int pf_census_device(const char *who, int task, int pb, unsigned long long first_cell, size_t count, const void *fmax_fast, const int *rmax_fast,
                      const void *fmax_exact, const int *rmax_exact, pf_census *out, size_t capacity, pf_census_cell *cells, hipStream_t st);
+// ---- pf_power.hip: power and smoothed variances of a resident spectrum; what it sees of a context (pf_api.hip) ----
+// this rank's ky-slab of a spectrum: rows [kx][ky_local] of nzp complex (nzp = nzh on the general path), ky = y0 + ky_local
+struct PfSpecView { const void *spec; int n, nzh, nzp, nyl, y0, fb, rank, P; hipStream_t stream; };
+void pf_ctx_spec_geometry(pf_ctx *c, PfSpecView *v);   // everything but `spec`
+// which: 0 delta(k), 1..3 the LPT source spectra, under the conditions of pf_get_density / pf_get_kvector (a pending x-transform of a
+// source is finished first, as that export does); refuses with the message of `who`
+int pf_ctx_spec_view(pf_ctx *c, const char *who, int which, PfSpecView *v);
+int pf_ctx_allreduce(pf_ctx *c, void *buf_dev, size_t count, int is_u64);   // the installed pf_allreduce_fn on the context's stream
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);
