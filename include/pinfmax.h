@@ -876,6 +876,28 @@ int pf_debug_strided_jobs(int field_bytes, int n, int njobs, int nin, const int 
 int pf_debug_strided_band(int field_bytes, int n, int njobs, int nin, const int *in_of, const int *mul, int nouter, int ncols,
                           int in_pitch, int out_pitch, int band_e, int band_outer, int outer_offset, int pre, double rs, double growth,
                           const double *in, double *out, int *guard_ok);
+/* test tap without a context: the z-pass c2r in the forms the library itself launches it (tests/test_gpu_zpass_forms.py) -- several jobs in
+   one launch, float / packed product rows, the fields' padded row pitches (spectra: n/2 + 64/field_bytes complex; real rows: twice that),
+   norm, a DC constant (dc: host pointer or NULL), in place or not, and the 3LPT(b) contraction inside the six-row z-pass.
+   form 0: njobs (1..6) jobs, job j with the kz factor mul[j] (0 one, 1 k, 2 k^2, 3 i k) and out_f32[j] (0: field-type rows at the fields'
+           pitch; 1: float rows of pitch n; 2: field-type rows of pitch n, fp64 fields only); in_place != 0 (every out_f32 == 0): each job's
+           result overwrites its own spectrum rows, as the Hessian z-pass does; otherwise every job has a buffer of its own.
+           spec [njobs][nrows][n/2+1] complex -> out [njobs][nrows][n]
+   form 1: the six jobs of the Hessian z-pass (kz factors one, one, k^2, one, k, k), nothing stored: acc -= 2 sum_ab phi2_ab hess_ab per cell,
+           hess [6][nrows][n] the first-order Hessian, acc [nrows][n] -> out [nrows][n]; form 2: the same with acc formed, not read, from
+           hess first (2 (h11 + h22 + h33) S2(h)); n a power of two.  mul, out_f32, njobs and in_place are ignored.
+   band: columns kz > band are not read (>= n/2: none); ncu: compute units the launch is sized for (0: the device's).
+   A size without such a kernel is an error (nothing is launched).  Every row's padding and a guard region behind every packed buffer
+   hold a byte pattern; *sentinel_ok = 1 when all of it -- and with form 1 / 2 the six hess fields as a whole -- came back unchanged. */
+int pf_debug_zpass_jobs(int field_bytes, int n, int form, int njobs, const int *mul, const int *out_f32, int in_place, int nrows, int band,
+                        double norm, const double *dc, int ncu, const double *spec, const double *hess, const double *acc, double *out,
+                        int *sentinel_ok);
+/* test tap without a context: the inverse x-pass that does the pending forward x-transform of its single input first (one rank, LPT
+   source spectra) into out_fused, and the two launches it replaces -- forward pass, then the plain inverse pass with the same jobs --
+   into out_plain.  in [nouter][n][ncols] complex, out_* [njobs][nouter][n][ncols]; mul, pre, rs, growth, outer_offset as in pf_debug_lines.
+   n a power of two up to 2048 (fp32 fields: below 1024). */
+int pf_debug_strided_xfuse(int field_bytes, int n, int njobs, const int *mul, int nouter, int ncols, int pre, double rs, double growth,
+                           int outer_offset, const double *in, double *out_fused, double *out_plain);
 /* how many sweeps of this context were repeated with six components per cell because the invariant z-pass met a tensor
    with q == 0 that is not exactly isotropic (the reference's "already diagonal" branch, src/collapse_times.c:722-727) */
 int pf_debug_invariant_reruns(pf_ctx *ctx);

@@ -269,6 +269,10 @@ PROTOTYPES = {
     "pf_debug_strided_jobs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, _dp, _dp]),
     "pf_debug_strided_band": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _dp, _dp, C.POINTER(C.c_int)]),
+    "pf_debug_zpass_jobs": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_double,
+                                      _dp, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
+    "pf_debug_strided_xfuse": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                         _dp, _dp, _dp]),
     "pf_debug_invariant_reruns": (C.c_int, [_vp]),
     "pf_solve_ran_beside_zpass": (C.c_int, [_vp]),
     "pf_transform_path": (C.c_int, [_vp]),

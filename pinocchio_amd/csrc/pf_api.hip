@@ -3030,6 +3030,200 @@ extern "C" int pf_debug_strided_band(int field_bytes, int n, int njobs, int nin,
   return rc;
 }
 
+// Test tap without a context: the z-pass c2r in the forms zpass_c2r() above launches it -- what pf_debug_lines (one job, F rows of pitch n,
+// norm = 1, no DC constant, MODE 0) does not reach.  The parameters are filled as zpass_c2r fills them and go to the production launchers:
+//   form 0: pf_launch_c2r with `njobs` jobs, mul[j] and out_f32[j] (0: F rows of pitch 2 nzp; 1: float rows of pitch n; 2: F rows of pitch n,
+//           fp64 fields only); every job has an output buffer of its own, or with in_place (every out_f32 == 0) its input rows themselves
+//   form 1 / 2: pf_launch_c2r_invariants MODE 1 / 2, six jobs with the kz factors of hess_yz: acc -= 2 phi2_ab h_ab (MODE 2: acc is formed)
+// Device rows: spectra at in_pitch = nzp = n / 2 + 64 / fb complex, F rows at 2 nzp reals (the library's own rule); the padding of every
+// row and a guard region behind every packed buffer hold bytes 0xa5.  *sentinel_ok = 1 when after the launch every byte outside the
+// rows' n output columns -- the padding, the guard regions, and with form 1 / 2 the six Hessian fields as a whole -- is what it was before.
+//   spec: [njobs][nrows][n/2+1] complex; hess: [6][nrows][n], acc: [nrows][n] (form 1 / 2)
+//   out:  form 0 [njobs][nrows][n]; form 1 / 2 [nrows][n], the updated acc
+extern "C" int pf_debug_zpass_jobs(int field_bytes, int n, int form, int njobs, const int *mul, const int *out_f32, int in_place, int nrows, int band,
+                                   double norm, const double *dc, int ncu, const double *spec, const double *hess, const double *acc, double *out,
+                                   int *sentinel_ok) {
+  static const int mul6[6] = {PF_MUL_ONE, PF_MUL_ONE, PF_MUL_K2, PF_MUL_ONE, PF_MUL_K, PF_MUL_K};
+  if (!spec || !out || !sentinel_ok || (field_bytes != 8 && field_bytes != 4) || n < 16 || n > 2048 || n % 2 || form < 0 || form > 2 || nrows < 1 ||
+      nrows > (1 << 20) || band < 0 || ncu < 0)
+    return pf_fail(0, "pf_debug_zpass_jobs: bad argument");
+  const int fb = field_bytes;
+  if (n & (n - 1)) {
+    PfMixedPlan pl;
+    if (!pf_mixed_supported(n) || !pf_mixed_plan(n / 2, true, &pl)) return pf_fail(0, "pf_debug_zpass_jobs: no stage plan for rows of %d points", n);
+  }
+  int f32[PF_MAX_JOBS], mu[PF_MAX_JOBS];
+  if (form == 0) {
+    if (!mul || !out_f32 || njobs < 1 || njobs > PF_MAX_JOBS) return pf_fail(0, "pf_debug_zpass_jobs: njobs");
+    for (int j = 0; j < njobs; j++) {
+      if (mul[j] < PF_MUL_ONE || mul[j] > PF_MUL_IK || out_f32[j] < 0 || out_f32[j] > 2) return pf_fail(0, "pf_debug_zpass_jobs: mul / out_f32");
+      if (out_f32[j] == 2 && fb != 8) return pf_fail(0, "pf_debug_zpass_jobs: double products go with fp64 fields");  // (as pf_create)
+      if (in_place && out_f32[j] != 0) return pf_fail(0, "pf_debug_zpass_jobs: only F rows of the fields' own pitch are written in place");
+      mu[j] = mul[j]; f32[j] = out_f32[j];
+    }
+  } else {
+    if (!hess || !acc) return pf_fail(0, "pf_debug_zpass_jobs: bad argument");
+    if (!pf_c2r_invariants_supported(fb, n) || (form == 2 && (n & (n - 1))))
+      return pf_fail(0, "pf_debug_zpass_jobs: no contracting z-pass (mode %d) for rows of %d points in fields of %d bytes", form, n, fb);
+    njobs = 6; in_place = 0;
+    for (int j = 0; j < 6; j++) { mu[j] = mul6[j]; f32[j] = 0; }
+  }
+  *sentinel_ok = 0;
+  pf_ctx *nc = nullptr;
+  const size_t nzh = (size_t)n / 2 + 1, nzp = (size_t)n / 2 + 64 / fb;           // c->nzh, c->nzp
+  const size_t R = (size_t)nrows, row_b = 2 * nzp * fb;                          // bytes of a device row: nzp complex = 2 nzp reals
+  const size_t field_b = R * row_b;
+  // output buffer of job j: rows of out_f32 == 0 lie at the fields' pitch, packed rows are followed by a guard of a row and more
+  auto out_rows_b = [&](int j) { return f32[j] == 0 ? field_b : R * n * (f32[j] == 1 ? 4 : fb); };
+  auto out_buf_b = [&](int j) { return f32[j] == 0 ? field_b : out_rows_b(j) + (size_t)n * 8 + 4096; };
+  void *d_in[PF_MAX_JOBS] = {}, *d_out[PF_MAX_JOBS] = {}, *d_acc = nullptr, *d_tw = nullptr; double *d_dc = nullptr;
+  int dev = 0;
+  {
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return pf_fail(0, "pf_debug_zpass_jobs: no HIP device");
+    if (ncu == 0) ncu = prop.multiProcessorCount;
+  }
+  PfTuning tune;
+  read_tuning(&tune);
+  std::vector<char> tw;
+  host_twiddles(n, fb, tw);
+  // host image of a field: `cnt` scalars per row from src (fp64) converted to F at the start of each row, 0xa5 everywhere else
+  auto image = [&](const double *src, size_t cnt, std::vector<unsigned char> &h) {
+    h.assign(field_b, 0xa5);
+    for (size_t r = 0; r < R; r++)
+      for (size_t k = 0; k < cnt; k++) {
+        if (fb == 8) ((double *)(h.data() + r * row_b))[k] = src[r * cnt + k];
+        else ((float *)(h.data() + r * row_b))[k] = (float)src[r * cnt + k];
+      }
+  };
+  auto body = [&]() -> int {
+    std::vector<unsigned char> h, before[PF_MAX_JOBS], acc_before, after;
+    for (int j = 0; j < njobs; j++) {
+      HIPCHK(nc, hipMalloc(&d_in[j], field_b));
+      image(spec + (size_t)j * R * nzh * 2, nzh * 2, h);
+      HIPCHK(nc, hipMemcpy(d_in[j], h.data(), field_b, hipMemcpyHostToDevice));
+      if (in_place) { d_out[j] = d_in[j]; before[j] = h; continue; }
+      HIPCHK(nc, hipMalloc(&d_out[j], out_buf_b(j)));
+      if (form == 0) before[j].assign(out_buf_b(j), 0xa5);
+      else image(hess + (size_t)j * R * n, (size_t)n, before[j]);
+      HIPCHK(nc, hipMemcpy(d_out[j], before[j].data(), before[j].size(), hipMemcpyHostToDevice));
+    }
+    if (form != 0) {
+      HIPCHK(nc, hipMalloc(&d_acc, field_b));
+      image(acc, (size_t)n, acc_before);
+      HIPCHK(nc, hipMemcpy(d_acc, acc_before.data(), field_b, hipMemcpyHostToDevice));
+    }
+    HIPCHK(nc, hipMalloc(&d_tw, tw.size()));
+    HIPCHK(nc, hipMemcpy(d_tw, tw.data(), tw.size(), hipMemcpyHostToDevice));
+    if (dc) {
+      HIPCHK(nc, hipMalloc((void **)&d_dc, sizeof(double)));
+      HIPCHK(nc, hipMemcpy(d_dc, dc, sizeof(double), hipMemcpyHostToDevice));
+    }
+    PfC2RParams p; memset(&p, 0, sizeof(p));
+    p.njobs = njobs;
+    for (int j = 0; j < njobs; j++) { p.job[j].in = d_in[j]; p.job[j].out = d_out[j]; p.job[j].mul = mu[j]; p.job[j].out_f32 = f32[j]; }
+    p.nlines = nrows; p.in_pitch = (long long)nzp; p.out_pitch = 2 * (long long)nzp;
+    p.norm = norm; p.dc = d_dc; p.tw = d_tw;
+    p.band_k = band < n / 2 ? band : n;
+    p.ncu = ncu; p.dev = dev; p.persist_per_cu = tune.zpass_persist; p.inv_per_cu = tune.zpass_inv_wg_per_cu;
+    if (form == 0) PFCHK0(pf_launch_c2r(fb, n, p, nullptr));
+    else { p.acc = d_acc; PFCHK0(pf_launch_c2r_invariants(fb, n, p, nullptr, form)); }
+    HIPCHK(nc, hipDeviceSynchronize());
+    int ok = 1;
+    // the n result columns of every row of `got` (scalars of `sb` bytes, rows `pitch_b` bytes apart) -> dst; everything else against `was`
+    auto collect = [&](const std::vector<unsigned char> &got, const std::vector<unsigned char> &was, size_t pitch_b, size_t sb, double *dst) {
+      for (size_t r = 0; r < R; r++) {
+        const unsigned char *g = got.data() + r * pitch_b;
+        if (dst) for (size_t k = 0; k < (size_t)n; k++) dst[r * n + k] = sb == 8 ? ((const double *)g)[k] : (double)((const float *)g)[k];
+        const size_t from = r * pitch_b + (dst ? (size_t)n * sb : 0), to = (r + 1) * pitch_b;
+        if (memcmp(got.data() + from, was.data() + from, to - from)) ok = 0;
+      }
+      if (got.size() > R * pitch_b && memcmp(got.data() + R * pitch_b, was.data() + R * pitch_b, got.size() - R * pitch_b)) ok = 0;
+    };
+    for (int j = 0; j < njobs; j++) {
+      after.resize(before[j].size());
+      HIPCHK(nc, hipMemcpy(after.data(), d_out[j], after.size(), hipMemcpyDeviceToHost));
+      if (form != 0) collect(after, before[j], row_b, fb, nullptr);               // the first-order Hessian: read only
+      else if (f32[j] == 0) collect(after, before[j], row_b, fb, out + (size_t)j * R * n);
+      else { const size_t sb = f32[j] == 1 ? 4 : fb; collect(after, before[j], (size_t)n * sb, sb, out + (size_t)j * R * n); }
+    }
+    if (form != 0) {
+      after.resize(field_b);
+      HIPCHK(nc, hipMemcpy(after.data(), d_acc, field_b, hipMemcpyDeviceToHost));
+      collect(after, acc_before, row_b, fb, out);
+    }
+    *sentinel_ok = ok;
+    return 0;
+  };
+  const int rc = body();
+  for (int j = 0; j < PF_MAX_JOBS; j++) { if (d_out[j] != d_in[j]) hipFree(d_out[j]); hipFree(d_in[j]); }
+  hipFree(d_acc); hipFree(d_tw); hipFree(d_dc);
+  return rc;
+}
+
+// Test tap without a context: the inverse x-pass with the forward x-transform of its (single, pending) input in front
+// (pf_launch_strided_xfuse, k_strided with PF_DIR_XF) beside the two launches it stands for -- the plain forward pass, then the plain
+// inverse pass with the same jobs on what that stored.  mul[j], pre / rs / growth / outer_offset as in pf_debug_lines.
+// in: [nouter][n][ncols]; out_fused, out_plain: [njobs][nouter][n][ncols]
+extern "C" int pf_debug_strided_xfuse(int field_bytes, int n, int njobs, const int *mul, int nouter, int ncols, int pre, double rs, double growth,
+                                      int outer_offset, const double *in, double *out_fused, double *out_plain) {
+  if (!in || !out_fused || !out_plain || !mul || njobs < 1 || njobs > PF_MAX_JOBS || nouter < 1 || ncols < 1 || (field_bytes != 8 && field_bytes != 4) ||
+      outer_offset < 0 || outer_offset >= n)
+    return pf_fail(0, "pf_debug_strided_xfuse: bad argument");
+  if (!pf_strided_xfuse_supported(field_bytes, n)) return pf_fail(0, "pf_debug_strided_xfuse: no fused x-pass for lines of %d points in fields of %d bytes", n, field_bytes);
+  const int fb = field_bytes, pc = (ncols + 15) & ~15;
+  pf_ctx *nc = nullptr;
+  const size_t nrows = (size_t)nouter * n, field = nrows * (size_t)pc * 2;  // scalars of one device field
+  void *d_in = nullptr, *d_mid = nullptr, *d_out = nullptr, *d_tw = nullptr; double *d_etab = nullptr;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return pf_fail(0, "pf_debug_strided_xfuse: no HIP device");
+  std::vector<char> tw;
+  host_twiddles(n, fb, tw);
+  auto body = [&]() -> int {
+    HIPCHK(nc, hipMalloc(&d_in, field * fb));
+    HIPCHK(nc, hipMalloc(&d_mid, field * fb));
+    HIPCHK(nc, hipMalloc(&d_out, (size_t)2 * njobs * field * fb));   // [fused, plain][njobs]
+    HIPCHK(nc, hipMalloc(&d_tw, tw.size()));
+    HIPCHK(nc, hipMalloc((void **)&d_etab, (size_t)n * sizeof(double)));
+    HIPCHK(nc, hipMemcpy(d_tw, tw.data(), tw.size(), hipMemcpyHostToDevice));
+    HIPCHK(nc, hipMemset(d_in, 0, field * fb));
+    HIPCHK(nc, hipMemset(d_mid, 0, field * fb));
+    HIPCHK(nc, hipMemset(d_out, 0, (size_t)2 * njobs * field * fb));
+    const size_t hrow = (size_t)ncols * 2 * fb, drow = (size_t)pc * 2 * fb, hfield = nrows * (size_t)ncols * 2;
+    std::vector<float> hf;
+    const void *src = in;
+    if (fb == 4) { hf.resize(hfield); for (size_t k = 0; k < hfield; k++) hf[k] = (float)in[k]; src = hf.data(); }
+    HIPCHK(nc, hipMemcpy2D(d_in, drow, src, hrow, hrow, nrows, hipMemcpyHostToDevice));
+    PfStridedParams p; memset(&p, 0, sizeof(p));
+    p.ain.os = (long long)n * pc; p.ain.el_shift = ilog2i(n); p.ain.el_len = n; p.ain.ehs = 0; p.ain.els = pc; p.aout = p.ain;
+    p.ncols = ncols; p.nouter = nouter; p.tw = d_tw; p.etab = d_etab; p.band_e = p.band_outer = n; p.dev = dev; p.outer_offset = outer_offset;
+    PfStridedParams q = p;                                            // the jobs of the inverse pass, as xpass() fills them
+    q.njobs = njobs; q.pre = pre ? 1 : 0; q.rs = rs; q.growth = growth;
+    if (pre && rs != 0.0) PFCHK0(pf_launch_exp_table(d_etab, n, rs, nullptr));
+    for (int j = 0; j < njobs; j++) { q.job[j].in = d_in; q.job[j].out = (char *)d_out + (size_t)j * field * fb; q.job[j].mul = mul[j]; }
+    PFCHK0(pf_launch_strided_xfuse(fb, n, q, nullptr));
+    p.njobs = 1; p.job[0].in = d_in; p.job[0].out = d_mid; p.job[0].mul = PF_MUL_ONE; p.growth = 1.0;
+    PFCHK0(pf_launch_strided(fb, n, -1, p, nullptr));
+    for (int j = 0; j < njobs; j++) { q.job[j].in = d_mid; q.job[j].out = (char *)d_out + (size_t)(njobs + j) * field * fb; }
+    PFCHK0(pf_launch_strided(fb, n, +1, q, nullptr));
+    HIPCHK(nc, hipDeviceSynchronize());
+    for (int j = 0; j < 2 * njobs; j++) {
+      double *dst = (j < njobs ? out_fused : out_plain) + (size_t)(j % njobs) * hfield;
+      const char *f = (const char *)d_out + (size_t)j * field * fb;
+      if (fb == 8) HIPCHK(nc, hipMemcpy2D(dst, hrow, f, drow, hrow, nrows, hipMemcpyDeviceToHost));
+      else {
+        hf.resize(hfield);
+        HIPCHK(nc, hipMemcpy2D(hf.data(), hrow, f, drow, hrow, nrows, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < hfield; k++) dst[k] = (double)hf[k];
+      }
+    }
+    return 0;
+  };
+  const int rc = body();
+  hipFree(d_in); hipFree(d_mid); hipFree(d_out); hipFree(d_tw); hipFree(d_etab);
+  return rc;
+}
+
 // used by pf_rccl.cpp
 extern "C" int pf_ctx_set_rccl(pf_ctx *c, void *link) {
   if (!c) return 1;
