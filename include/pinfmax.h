@@ -1022,6 +1022,67 @@ int pf_debug_power_spectrum(int field_bytes, int n, int y0, int nyl, const doubl
                             double *variance, pf_power_info *info);
 int pf_debug_power_times(double *ms);
 
+/* --- matter density of the LPT-displaced particles and its spectra ---
+   What the reference checks its mode 3 with (the auto and cross power of the particle density against the linear field, the plots
+   under tests/ICs_piti_vs_pinocchio), from the twelve displacement columns in HBM: cloud-in-cell assignment of one particle per
+   cell, the density contrast, the context's forward transform, and shell sums with the resident delta(k).  Mass assignment and
+   spectra have no counterpart in the reference's code; the positions are its initialize_POS (src/write_snapshot.c:907-954).
+   Position of the particle of global cell (q0, q1, q2), axis j, PRODFLOAT T, columns k = j, 3 + j, 6 + j, 9 + j of vel12 (those of
+     LPT orders the context does not compute read zero):
+       pos = (T)((double)q_j + 0.5 + (double)V1);  pos = pos + V2;  pos = pos + (V31 + V32);
+       if (pos >= (T)n) pos -= (T)n;  if (pos < 0) pos += (T)n;                         (once, in T arithmetic)
+     weight != NULL: each column value v of order k (0 Zel'dovich, 1 2LPT, 2 3LPT(a), 3 3LPT(b)) is first replaced by
+     (T)(weight[k] (double)v) -- {1,0,0,0} gives the Zel'dovich positions, {1,1,0,0} 2LPT, from the same columns.
+   A particle with a position that is not finite on any axis is counted in info->nonfinite, one outside [0, n] after the single wrap
+     in info->outside; neither is deposited.  The others are counted in info->deposited.
+   CIC in integers: u = pos - 0.5, i0 = floor(u), d = u - i0, t = (uint32)(d 65536) truncated; weight 65536 - t to cell i0 mod n and
+     t to (i0 + 1) mod n; the eight contributions are the products of three such factors as 64-bit integers, so every deposited
+     particle adds exactly 2^48 and the grid is the same bits for any order of the additions.  Headroom: fewer than 2^16 whole
+     particles may meet in one cell (info->max_cell, in units of 2^-48 particle, says how close a call came).
+     PF_MATTER_NGP: the whole 2^48 to the cell floor(pos) mod n.
+   delta = cell / 2^48 - 1 in double, rounded once to the field type.  info->empty_cells, info->max_cell and
+     info->sum_hi32 2^32 + info->sum_lo32 = deposited 2^48 (the sums of the high and low 32 bits of the cells) come from the same pass.
+   density_host != NULL: delta of this rank's slab [nxl][n][n] as the transform reads it, widened to fp64.
+   Shells, weights, nmodes and k2sum: exactly pf_power_spectrum's.  power[b] = sum of w |delta_m|^2 / N^6.  cross != NULL:
+     cross[b] = (sum of the positive terms w Re(delta_m conj delta) - sum of the negated negative ones) / N^6 with the resident
+     delta(k), each of the two a fixed-point sum of its own, the difference formed once in double.  Parts are widened to double
+     first; |delta_m|^2 = re^2 + im^2 and Re(..) = re_m re + im_m im are two products and a sum, each rounded once.
+     PF_MATTER_DECONVOLVE: every term carries (c[|kx|] c[|ky|]) c[kz], c[j] = sinc(pi j / n)^(-p), p = 1 for NGP and 2 for CIC,
+     squared for power and once for cross.  info->nonfinite_modes: modes (counted with w) with a term that is not finite: in nmodes
+     and k2sum and in no other sum.  info->modes = n^3.  No floating-point atomics: the bits are the same for any launch geometry.
+   One rank only: particles leave their x-slab.  Every transform path, both field and both product types.
+   The grid (8 bytes per cell) and the tables are allocated for the call and freed before it returns; delta and its spectrum live in
+     the scratch field of the transform taps (pf_forward_transform).  pf_device_bytes, the products, the resident spectra, the
+     arithmetic setting and every state flag are as before.
+   Refused (1, pf_last_error, nothing launched): null ctx / nmodes / k2sum / power / info, unknown flag bits, a weight that is not
+     finite, products not computed, cross != NULL without a density, more than one rank, a failed allocation (with the bytes).
+   pf_debug_matter_deposit: test tap without a context, the production deposit on a caller's columns [12][n^3] of pb-byte
+     PRODFLOATs (x0 = 0, nxl = n) -> the grid [n^3] and the counters of info (modes = 0).
+   pf_debug_matter_shells: the production shell passes on the rows y0 .. y0 + nyl - 1 of two caller's spectra, ky-slabs
+     [nyl][n (kx)][n/2+1][2] in fp64 converted to field_bytes on the way in; spec_lin (and cross) may be NULL.
+   PF_MATTER_LDS (environment, read per call; default 1): the deposit stages bricks of 4 x 4 x 16 particles in an LDS tile where n is a
+     multiple of 16 and nxl one of 4; 0, or any other grid: one particle per lane straight into the grid.  The grids are identical.
+   pf_debug_matter_times: with PF_MATTER_TIMES=1 in the environment, ms[0..3] = device ms of the deposit (with the clearing of the
+     grid), the contrast, the transform and the shell passes of the calling thread's last call; 0 otherwise.
+   pf_debug_matter_form: what the calling thread's last call launched -- form[0] = the deposit (0 one particle per lane, 1 LDS-staged,
+     -1 none yet), form[1] = the scans of its shell passes (1: one scan for the three sums, 3: a scan per sum -- grids above about
+     1800, or PF_MATTER_SCAN_EACH=1, which the tests use to reach that way on a small grid; 0 none yet). */
+#define PF_MATTER_NGP 1
+#define PF_MATTER_DECONVOLVE 2
+typedef struct {
+  unsigned long long deposited, nonfinite, outside, empty_cells, max_cell, sum_hi32, sum_lo32, modes, nonfinite_modes;
+} pf_matter_info;
+int pf_matter_power(pf_ctx *ctx, int flags, const double *weight,
+                    unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross,
+                    double *density_host, pf_matter_info *info);
+int pf_debug_matter_deposit(int pb, int n, const void *vel12_host, int flags, const double *weight,
+                            unsigned long long *grid_host, pf_matter_info *info);
+int pf_debug_matter_shells(int field_bytes, int n, int y0, int nyl, const double *spec_m, const double *spec_lin,
+                           int flags, unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross,
+                           pf_matter_info *info);
+int pf_debug_matter_times(double *ms);
+int pf_debug_matter_form(int *form);
+
 /* --- measurement --- */
 int pf_get_cputime(pf_ctx *ctx, pf_cputime *t);
 int pf_reset_cputime(pf_ctx *ctx);

@@ -135,6 +135,13 @@ class PowerInfo(C.Structure):
     _fields_ = [("modes", C.c_ulonglong), ("nonfinite", C.c_ulonglong)]
 
 
+MATTER_NGP, MATTER_DECONVOLVE = 1, 2   # PF_MATTER_*
+
+
+class MatterInfo(C.Structure):
+    _fields_ = [(k, C.c_ulonglong) for k in ("deposited", "nonfinite", "outside", "empty_cells", "max_cell", "sum_hi32", "sum_lo32", "modes", "nonfinite_modes")]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -304,6 +311,12 @@ PROTOTYPES = {
     "pf_debug_power_spectrum": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _dp, _dp,
                                           C.POINTER(PowerInfo)]),
     "pf_debug_power_times": (C.c_int, [_dp]),
+    "pf_matter_power": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _dp, _dp, _dp, C.POINTER(MatterInfo)]),
+    "pf_debug_matter_deposit": (C.c_int, [C.c_int, C.c_int, _vp, C.c_int, _dp, C.POINTER(C.c_ulonglong), C.POINTER(MatterInfo)]),
+    "pf_debug_matter_shells": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _dp, _dp,
+                                         C.POINTER(MatterInfo)]),
+    "pf_debug_matter_times": (C.c_int, [_dp]),
+    "pf_debug_matter_form": (C.c_int, [C.POINTER(C.c_int)]),
     "pf_get_cputime": (C.c_int, [_vp, C.POINTER(CpuTime)]),
     "pf_reset_cputime": (C.c_int, [_vp]),
     "pf_kernel_stats": (C.c_int, [_vp, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),

@@ -126,6 +126,76 @@ def debug_power_spectrum(spec, y0: int = 0, field_bytes: int = 8, radii_cells=()
     return out
 
 
+MATTER_NGP, MATTER_DECONVOLVE = _lib.MATTER_NGP, _lib.MATTER_DECONVOLVE
+
+
+def matter_times():
+    """device ms of the last matter_power / debug_matter_*: (deposit, contrast, transform, shell sums); zeros without PF_MATTER_TIMES=1
+    (pf_debug_matter_times)"""
+    ms = (C.c_double * 4)()
+    _lib.load().pf_debug_matter_times(ms)
+    return tuple(float(x) for x in ms)
+
+
+def matter_form():
+    """what the calling thread's last matter call launched: (deposit: 0 one particle per lane, 1 LDS-staged, -1 none yet; scans of its
+    shell passes: 1, 3, or 0 for none yet) (pf_debug_matter_form)"""
+    form = (C.c_int * 2)()
+    _lib.load().pf_debug_matter_form(form)
+    return int(form[0]), int(form[1])
+
+
+def _matter_flags(ngp, deconvolve):
+    return (MATTER_NGP if ngp else 0) | (MATTER_DECONVOLVE if deconvolve else 0)
+
+
+def _matter_info(info):
+    return {k: int(getattr(info, k)) for k, _ in info._fields_}
+
+
+def debug_matter_deposit(vel12, ngp: bool = False, weight=None):
+    """the production deposit on a caller's columns [12][n][n][n], float32 or float64 (pf_debug_matter_deposit) -> (the grid
+    [n][n][n] of uint64 in units of 2^-48 particle, the dict of pf_matter_info)"""
+    L = _lib.load()
+    vel12 = np.ascontiguousarray(vel12)
+    if vel12.dtype not in (np.float32, np.float64) or vel12.ndim != 4 or vel12.shape[0] != 12 or len(set(vel12.shape[1:])) != 1:
+        raise ValueError(f"columns [12][n][n][n] of float32 or float64, not {vel12.dtype} {vel12.shape}")
+    n = vel12.shape[1]
+    w = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64).reshape(4)
+    grid = np.zeros((n, n, n), dtype=np.uint64)
+    info = _lib.MatterInfo()
+    if L.pf_debug_matter_deposit(vel12.dtype.itemsize, n, vel12.ctypes.data_as(C.c_void_p), _matter_flags(ngp, False), None if w is None else _dp(w),
+                                 grid.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(info)):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_matter_deposit failed")
+    return grid, _matter_info(info)
+
+
+def debug_matter_shells(spec_m, spec_lin=None, y0: int = 0, field_bytes: int = 8, ngp: bool = False, deconvolve: bool = False):
+    """the production shell passes on the rows y0 .. y0 + nyl - 1 of two spectra, ky-slabs [nyl][n (kx)][n/2+1] complex128
+    (pf_debug_matter_shells) -> nmodes[], k2sum[], power[], cross[] (None without spec_lin) and the counters of pf_matter_info"""
+    L = _lib.load()
+    spec_m = np.ascontiguousarray(spec_m, dtype=np.complex128)
+    if spec_m.ndim != 3 or spec_m.shape[2] != spec_m.shape[1] // 2 + 1:
+        raise ValueError(f"a ky-slab [nyl][n][n/2+1], not {spec_m.shape}")
+    if spec_lin is not None:
+        spec_lin = np.ascontiguousarray(spec_lin, dtype=np.complex128)
+        if spec_lin.shape != spec_m.shape:
+            raise ValueError(f"two slabs of one shape, not {spec_m.shape} and {spec_lin.shape}")
+    nyl, n = spec_m.shape[:2]
+    nb = int(L.pf_power_bins(n))
+    nm, k2 = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.uint64)
+    pw, cr = np.zeros(nb), np.zeros(nb)
+    info = _lib.MatterInfo()
+    up = lambda a: a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+    two = spec_lin is not None
+    if L.pf_debug_matter_shells(int(field_bytes), n, int(y0), nyl, _dp(spec_m.view(np.float64)), _dp(spec_lin.view(np.float64)) if two else None,
+                                _matter_flags(ngp, deconvolve), up(nm), up(k2), _dp(pw), _dp(cr) if two else None, C.byref(info)):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_matter_shells failed")
+    out = {"nmodes": nm, "k2sum": k2, "power": pw, "cross": cr if two else None}
+    out.update(_matter_info(info))
+    return out
+
+
 _ARITH = {"fast": _lib.ARITH_FAST, "exact": _lib.ARITH_EXACT}
 # pf_census_cell: an outlier of the flavour census
 CENSUS_CELL_DTYPE = np.dtype([("cell", "<u8"), ("fast", "<f8"), ("exact", "<f8"), ("rmax_fast", "<i4"), ("rmax_exact", "<i4")], align=False)
@@ -1347,6 +1417,32 @@ class Fmax:
             with np.errstate(invalid="ignore", divide="ignore"):
                 out["k"] = (2.0 * np.pi / float(box)) * np.sqrt(out["k2sum"].astype(np.float64) / nm)
                 out["pk"] = out["power"] / nm * float(box) ** 3
+        return out
+
+    def matter_power(self, weight=None, cross: bool = True, density: bool = False, ngp: bool = False, deconvolve: bool = False, box=None) -> dict:
+        """the density of the particles at their LPT positions and its shell sums (pf_matter_power; one rank): cloud-in-cell (or
+        nearest-grid-point) assignment of the displacement columns in HBM, optionally weighted per LPT order (`weight`, four
+        factors: (1, 0, 0, 0) is Zel'dovich alone), the forward transform, and per shell nmodes[], k2sum[], power[] = sum of w
+        |delta_m|^2 / N^6 and, with `cross`, cross[] = sum of w Re(delta_m conj delta) / N^6 with the resident delta(k) -> those,
+        the counters of pf_matter_info, with `density` the contrast [nxl][n][n] the transform read, and with the box length `box`
+        k, pk and pk_cross per shell as power_spectrum forms them"""
+        nb = int(self.L.pf_power_bins(self.n))
+        nm, k2 = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.uint64)
+        pw, cr = np.zeros(nb), np.zeros(nb)
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64).reshape(4)
+        dens = np.zeros((self.nxl, self.n, self.n)) if density else None
+        info = _lib.MatterInfo()
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+        self._chk(self.L.pf_matter_power(self.h, _matter_flags(ngp, deconvolve), None if w is None else _dp(w), up(nm), up(k2), _dp(pw), _dp(cr) if cross else None,
+                                         _dp(dens) if density else None, C.byref(info)))
+        out = {"nmodes": nm, "k2sum": k2, "power": pw, "cross": cr if cross else None, "density": dens}
+        out.update(_matter_info(info))
+        if box is not None:
+            f = nm.astype(np.float64)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                out["k"] = (2.0 * np.pi / float(box)) * np.sqrt(k2.astype(np.float64) / f)
+                out["pk"] = pw / f * float(box) ** 3
+                out["pk_cross"] = cr / f * float(box) ** 3 if cross else None
         return out
 
     # -- measurement ------------------------------------------------------

@@ -2588,6 +2588,10 @@ static int export_real(pf_ctx *c, const void *src, double *host) {
   PFCHK(c, pf_launch_real_export(c->fb, src, (double *)staging(c), nrows, c->n, rpitch(c), c->stream));
   return handoff_d2h(c, (char *)host, staging(c), (size_t)nrows * c->n * sizeof(double), 1, no_fill);
 }
+// what pf_matter.hip sees of a context (pf_internal.h): the field of the transform taps below, which no later call reads
+void pf_ctx_matter_view(pf_ctx *c, PfMatterCtx *m) { m->field = c->A[0]; m->rpitch = rpitch(c); m->x0 = c->rank * c->nxl; m->lpt_order = c->lpt_order; }
+int pf_ctx_matter_forward(pf_ctx *c) { return forward_of(c, c->A[0]); }
+int pf_ctx_matter_export(pf_ctx *c, double *host) { return export_real(c, c->A[0], host); }
 extern "C" int pf_forward_transform(pf_ctx *c, const double *real_host, double *spec_host) {
   if (!c || !real_host || !spec_host) return 1;
   // P > 1: the y-pass writes the send blocks into A[0], so the field itself lives in receive field 0

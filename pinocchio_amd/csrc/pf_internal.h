@@ -381,6 +381,13 @@ void pf_ctx_spec_geometry(pf_ctx *c, PfSpecView *v);   // everything but `spec`
 // source is finished first, as that export does); refuses with the message of `who`
 int pf_ctx_spec_view(pf_ctx *c, const char *who, int which, PfSpecView *v);
 int pf_ctx_allreduce(pf_ctx *c, void *buf_dev, size_t count, int is_u64);   // the installed pf_allreduce_fn on the context's stream
+// ---- pf_matter.hip: the density of the displaced particles and its spectra; what it sees of a context beside the views above ----
+// field: the scratch field of the transform taps (real rows of rpitch reals, then its spectrum in the layout of PfSpecView); x0: global x
+// of the first local plane; lpt_order: the LPT order whose columns are computed (the others read zero)
+struct PfMatterCtx { void *field; long long rpitch; int x0, lpt_order; };
+void pf_ctx_matter_view(pf_ctx *c, PfMatterCtx *m);
+int pf_ctx_matter_forward(pf_ctx *c);                 // the context's forward transform of that field, in place
+int pf_ctx_matter_export(pf_ctx *c, double *host);    // its real rows -> [nxl][n][n] fp64 on the host (through the staging fields)
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);
