@@ -1050,7 +1050,7 @@ int pf_debug_power_times(double *ms);
      PF_MATTER_DECONVOLVE: every term carries (c[|kx|] c[|ky|]) c[kz], c[j] = sinc(pi j / n)^(-p), p = 1 for NGP and 2 for CIC,
      squared for power and once for cross.  info->nonfinite_modes: modes (counted with w) with a term that is not finite: in nmodes
      and k2sum and in no other sum.  info->modes = n^3.  No floating-point atomics: the bits are the same for any launch geometry.
-   One rank only: particles leave their x-slab.  Every transform path, both field and both product types.
+   One rank only: particles leave their x-slab (pf_matter_power_slabs below is the collective call).  Every transform path, both field and both product types.
    The grid (8 bytes per cell) and the tables are allocated for the call and freed before it returns; delta and its spectrum live in
      the scratch field of the transform taps (pf_forward_transform).  pf_device_bytes, the products, the resident spectra, the
      arithmetic setting and every state flag are as before.
@@ -1082,6 +1082,55 @@ int pf_debug_matter_shells(int field_bytes, int n, int y0, int nyl, const double
                            pf_matter_info *info);
 int pf_debug_matter_times(double *ms);
 int pf_debug_matter_form(int *form);
+
+/* --- the same on any number of ranks: pf_matter_power_slabs ---
+   pf_matter_power for a context of P x-slabs, collective over its ranks like pf_power_spectrum: ON ANY NUMBER OF RANKS EVERY RANK
+   RECEIVES EXACTLY THE BITS ONE RANK RETURNS FOR THE SAME BOX.  Arguments, flags, positions, integer CIC / NGP, contrast, shells,
+   deconvolution and weight are pf_matter_power's, word for word; every rank passes the same flags and weight.  nmodes, k2sum, power
+   and cross are the box's on every rank; density_host is this rank's slab [nxl][n][n]; info is the box's: deposited, nonfinite,
+   outside, empty_cells, sum_hi32, sum_lo32 and nonfinite_modes summed over the ranks, max_cell the largest over the ranks,
+   modes = n^3.
+   The particles of a slab leave it, so:
+     reach     one pass over the four x columns (k_matter_reach): of every particle whose x position is finite and inside [0, n] the
+               x planes it adds to (CIC: i0 and, where its weight t is not zero, i0 + 1; NGP: floor(pos)) as signed minimal-image
+               offsets s = ((plane - q0 + n/2) mod n) - n/2 from its own plane q0; Hlo = max(0, -min s), Hhi = max(0, max s).  A
+               particle that only its y or z position keeps out of the grid still counts: a window can be a plane wider than
+               needed, never narrower.  The ranks agree on the largest Hlo and Hhi (first all-reduce).
+     window    every rank deposits its own particles into the planes [x0 - Hlo, x0 + nxl + Hhi) (mod n), or into the whole box once
+               nxl + Hlo + Hhi >= n: nothing a particle adds falls outside.
+     exchange  plane g belongs to rank g / nxl.  Rank r sends rank q != r a block of B planes, slot j the j-th (ascending local index)
+               plane of q inside the window of r; B is the longest such list over all pairs, found by every rank from (n, P, Hlo, Hhi)
+               alone.  ONE call of the context's all-to-all (pf_set_exchange / pf_init_rccl / the fabric), bytes_per_peer = 8 B n^2;
+               the owner adds the filled slots to its planes (k_matter_fold: 64-bit integer adds, no atomics).  The uniform
+               all-to-all carries P B planes per rank of which only those of the neighbours are filled.  Hlo = Hhi = 0, or one
+               rank: no exchange.
+     spectra   the contrast of the rank's own planes goes into the field the slab transform reads (receive field 0 with more than
+               one rank, as in pf_forward_transform); the scans' maxima of every shell are taken over the ranks, then every rank
+               adds its limbs under the box's exponent and the integer tables are summed over the ranks: the sums of the one-rank call.
+   The installed all-reduce only sums: a maximum over the ranks is the sum of vectors in which every rank fills its own slot.
+   Memory: (wn + 2 P B) n^2 8 bytes (wn = nxl + Hlo + Hhi, at most n: the window, the send and the receive blocks) and the tables,
+     allocated for the call and freed before it returns.  pf_device_bytes, the products, the resident spectra, the arithmetic
+     setting and every state flag are as before; a sweep after the call gives what it gave before.
+   With one rank the call is pf_matter_power bit for bit, with the reach pass in front and no exchange.
+   Refused (1, pf_last_error names pf_matter_power_slabs) as pf_matter_power refuses, except for the number of ranks, and: more
+     than one rank without an installed all-to-all and all-reduce; an odd grid on more than one rank.  A rank that refuses on its
+     own tells the others in the first all-reduce: every rank returns 1 and nothing but the reach pass of the other ranks was
+     launched.  A failed allocation (message with the bytes) is agreed on in a second all-reduce, before any rank enters the all-to-all.
+   pf_debug_matter_times: the reach pass, pack, exchange and fold count to ms[0] (deposit).
+   pf_debug_matter_slabs: collective test tap on a live context of any rank count: the production reach pass, deposit, exchange and
+     fold on the caller's columns [12][nxl*n*n] of this rank's slab (PRODFLOATs of the context's product type) -> this rank's planes
+     of the grid [nxl][n][n] and the box's counters in info (modes = 0).  Needs no density, no products; leaves the context as it
+     found it.
+   pf_debug_matter_exchange: what the calling thread's last pf_matter_power_slabs / pf_debug_matter_slabs did: out[0] = form (0 no
+     exchange: one rank or reach 0 both ways, 1 ghost planes, 2 every rank deposits the whole box), out[1] / out[2] = reach below /
+     above in planes (common to all ranks), out[3] = planes of the deposit window, out[4] = planes per peer block, out[5] =
+     bytes_per_peer handed to the all-to-all (0 without an exchange). */
+int pf_matter_power_slabs(pf_ctx *ctx, int flags, const double *weight,
+                          unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross,
+                          double *density_host, pf_matter_info *info);
+int pf_debug_matter_slabs(pf_ctx *ctx, const void *vel12_slab_host, int flags, const double *weight,
+                          unsigned long long *grid_slab_host, pf_matter_info *info);
+int pf_debug_matter_exchange(unsigned long long out[6]);
 
 /* --- measurement --- */
 int pf_get_cputime(pf_ctx *ctx, pf_cputime *t);

@@ -317,6 +317,9 @@ PROTOTYPES = {
                                          C.POINTER(MatterInfo)]),
     "pf_debug_matter_times": (C.c_int, [_dp]),
     "pf_debug_matter_form": (C.c_int, [C.POINTER(C.c_int)]),
+    "pf_matter_power_slabs": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _dp, _dp, _dp, C.POINTER(MatterInfo)]),
+    "pf_debug_matter_slabs": (C.c_int, [_vp, _vp, C.c_int, _dp, C.POINTER(C.c_ulonglong), C.POINTER(MatterInfo)]),
+    "pf_debug_matter_exchange": (C.c_int, [C.POINTER(C.c_ulonglong)]),
     "pf_get_cputime": (C.c_int, [_vp, C.POINTER(CpuTime)]),
     "pf_reset_cputime": (C.c_int, [_vp]),
     "pf_kernel_stats": (C.c_int, [_vp, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),

@@ -145,6 +145,18 @@ def matter_form():
     return int(form[0]), int(form[1])
 
 
+EXCHANGE_KEYS = ("form", "reach_below", "reach_above", "window_planes", "block_planes", "bytes_per_peer")
+
+
+def matter_exchange():
+    """what the calling thread's last matter_power_slabs / debug_matter_slabs did (pf_debug_matter_exchange): form (0 no exchange,
+    1 ghost planes, 2 every rank deposits the whole box), the common reach below / above in planes, the planes of the deposit window
+    and of a peer block, and the bytes per peer handed to the all-to-all"""
+    out = (C.c_ulonglong * 6)()
+    _lib.load().pf_debug_matter_exchange(out)
+    return dict(zip(EXCHANGE_KEYS, (int(x) for x in out)))
+
+
 def _matter_flags(ngp, deconvolve):
     return (MATTER_NGP if ngp else 0) | (MATTER_DECONVOLVE if deconvolve else 0)
 
@@ -1444,6 +1456,45 @@ class Fmax:
                 out["pk"] = pw / f * float(box) ** 3
                 out["pk_cross"] = cr / f * float(box) ** 3 if cross else None
         return out
+
+    def matter_power_slabs(self, weight=None, cross: bool = True, density: bool = False, ngp: bool = False, deconvolve: bool = False, box=None) -> dict:
+        """matter_power on any number of ranks (pf_matter_power_slabs; collective: every rank calls it with the same arguments): the
+        particles that leave a slab reach their planes through one all-to-all of the context, and every rank receives the bits one
+        rank returns for the same box -> the dict of matter_power, the columns and counters the box's, `density` this rank's slab,
+        and `exchange`, what crossed (matter_exchange())"""
+        nb = int(self.L.pf_power_bins(self.n))
+        nm, k2 = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.uint64)
+        pw, cr = np.zeros(nb), np.zeros(nb)
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64).reshape(4)
+        dens = np.zeros((self.nxl, self.n, self.n)) if density else None
+        info = _lib.MatterInfo()
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+        self._chk(self.L.pf_matter_power_slabs(self.h, _matter_flags(ngp, deconvolve), None if w is None else _dp(w), up(nm), up(k2), _dp(pw),
+                                               _dp(cr) if cross else None, _dp(dens) if density else None, C.byref(info)))
+        out = {"nmodes": nm, "k2sum": k2, "power": pw, "cross": cr if cross else None, "density": dens, "exchange": matter_exchange()}
+        out.update(_matter_info(info))
+        if box is not None:
+            f = nm.astype(np.float64)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                out["k"] = (2.0 * np.pi / float(box)) * np.sqrt(k2.astype(np.float64) / f)
+                out["pk"] = pw / f * float(box) ** 3
+                out["pk_cross"] = cr / f * float(box) ** 3 if cross else None
+        return out
+
+    def debug_matter_slabs(self, vel12_slab, ngp: bool = False, weight=None):
+        """collective test tap (pf_debug_matter_slabs): the production reach pass, deposit, exchange and fold on the caller's columns
+        [12][nxl][n][n] of this rank's slab, in the context's product type -> (this rank's planes of the grid [nxl][n][n] of uint64,
+        the dict of pf_matter_info for the box)"""
+        T = np.float64 if self.double_products else np.float32
+        v = np.ascontiguousarray(vel12_slab)
+        if v.dtype != T or v.shape != (12, self.nxl, self.n, self.n):
+            raise ValueError(f"columns [12][{self.nxl}][{self.n}][{self.n}] of {np.dtype(T).name}, not {v.dtype} {v.shape}")
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64).reshape(4)
+        grid = np.zeros((self.nxl, self.n, self.n), dtype=np.uint64)
+        info = _lib.MatterInfo()
+        self._chk(self.L.pf_debug_matter_slabs(self.h, v.ctypes.data_as(C.c_void_p), _matter_flags(ngp, False), None if w is None else _dp(w),
+                                               grid.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(info)))
+        return grid, _matter_info(info)
 
     # -- measurement ------------------------------------------------------
     def cputime(self) -> dict:

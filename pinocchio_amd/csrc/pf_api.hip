@@ -2576,6 +2576,14 @@ int pf_ctx_spec_view(pf_ctx *c, const char *who, int which, PfSpecView *v) {
   return 0;
 }
 int pf_ctx_allreduce(pf_ctx *c, void *buf_dev, size_t count, int is_u64) { return allreduce_dev(c, buf_dev, count, is_u64); }
+int pf_ctx_alltoall(pf_ctx *c, const void *send_dev, void *recv_dev, size_t bytes_per_peer) {
+  if (c->P == 1) return 0;
+  if (!c->a2a) return pf_fail(c->rank, "no exchange installed for %d ranks (pf_set_exchange / pf_init_rccl)", c->P);
+  KTimer t(c, KS_EXCHANGE, (double)bytes_per_peer * c->P, c->stream);
+  if (c->a2a(c->a2a_user, send_dev, recv_dev, bytes_per_peer, (void *)c->stream)) return pf_fail(c->rank, "all-to-all failed");
+  return 0;
+}
+int pf_ctx_exchange_installed(pf_ctx *c) { return c->P == 1 || (c->a2a && c->ared); }
 
 static int import_real(pf_ctx *c, const double *host, void *dst) {
   const long long nrows = (long long)c->nxl * c->n;
@@ -2589,9 +2597,11 @@ static int export_real(pf_ctx *c, const void *src, double *host) {
   return handoff_d2h(c, (char *)host, staging(c), (size_t)nrows * c->n * sizeof(double), 1, no_fill);
 }
 // what pf_matter.hip sees of a context (pf_internal.h): the field of the transform taps below, which no later call reads
-void pf_ctx_matter_view(pf_ctx *c, PfMatterCtx *m) { m->field = c->A[0]; m->rpitch = rpitch(c); m->x0 = c->rank * c->nxl; m->lpt_order = c->lpt_order; }
-int pf_ctx_matter_forward(pf_ctx *c) { return forward_of(c, c->A[0]); }
-int pf_ctx_matter_export(pf_ctx *c, double *host) { return export_real(c, c->A[0], host); }
+// (P > 1: receive field 0, as in pf_forward_transform below -- the y-pass writes the send blocks into A[0])
+static void *matter_field(pf_ctx *c) { return c->P > 1 ? recv_field(c, 0, 0) : c->A[0]; }
+void pf_ctx_matter_view(pf_ctx *c, PfMatterCtx *m) { m->field = matter_field(c); m->rpitch = rpitch(c); m->x0 = c->rank * c->nxl; m->lpt_order = c->lpt_order; }
+int pf_ctx_matter_forward(pf_ctx *c) { return forward_of(c, matter_field(c)); }
+int pf_ctx_matter_export(pf_ctx *c, double *host) { return export_real(c, matter_field(c), host); }
 extern "C" int pf_forward_transform(pf_ctx *c, const double *real_host, double *spec_host) {
   if (!c || !real_host || !spec_host) return 1;
   // P > 1: the y-pass writes the send blocks into A[0], so the field itself lives in receive field 0

@@ -381,8 +381,12 @@ void pf_ctx_spec_geometry(pf_ctx *c, PfSpecView *v);   // everything but `spec`
 // source is finished first, as that export does); refuses with the message of `who`
 int pf_ctx_spec_view(pf_ctx *c, const char *who, int which, PfSpecView *v);
 int pf_ctx_allreduce(pf_ctx *c, void *buf_dev, size_t count, int is_u64);   // the installed pf_allreduce_fn on the context's stream
+// the installed pf_alltoall_fn on the context's stream: block q of send_dev goes to rank q, block p of recv_dev comes from rank p
+int pf_ctx_alltoall(pf_ctx *c, const void *send_dev, void *recv_dev, size_t bytes_per_peer);
+int pf_ctx_exchange_installed(pf_ctx *c);   // one rank, or both an all-to-all and an all-reduce are installed
 // ---- pf_matter.hip: the density of the displaced particles and its spectra; what it sees of a context beside the views above ----
-// field: the scratch field of the transform taps (real rows of rpitch reals, then its spectrum in the layout of PfSpecView); x0: global x
+// field: the scratch field of the transform taps (real rows of rpitch reals, then its spectrum in the layout of PfSpecView; with more
+// than one rank that is receive field 0, the field pf_forward_transform uses there); x0: global x
 // of the first local plane; lpt_order: the LPT order whose columns are computed (the others read zero)
 struct PfMatterCtx { void *field; long long rpitch; int x0, lpt_order; };
 void pf_ctx_matter_view(pf_ctx *c, PfMatterCtx *m);

@@ -21,9 +21,11 @@
 //                     maximum (LDS holds one sum's counters, so every grid up to 2048 fits).  Four passes over the two spectra
 //                     (profiles/matter_notes.md).
 //  k_matter_final     limbs -> double, times 1 / N^6; cross = positive - negative, formed once.
+//  k_matter_reach /   pf_matter_power_slabs, the call on more than one rank (at the end of this file): how many planes the particles of
+//  k_matter_fold      a slab reach beyond it, and the 64-bit integer add of the ghost planes the other ranks sent into the owner's planes.
 //
 // Every index is in range by construction: a particle index is below ncell; a target plane is wrapped into [0, n) and deposited only
-// when it lies in this slab's [x0, x0 + nxl) (always, with one rank); target rows and columns are wrapped into [0, n); a mode is read
+// when its window plane (plane - w0) mod n is below wn, the planes the grid was allocated with (always, with one rank); target rows and columns are wrapped into [0, n); a mode is read
 // at a row below `rows` and a column kz <= n/2 < pitch; a shell is below pf_power_nbins(n), which sized every table; the
 // deconvolution table is read at |kx|, |ky|, kz <= n/2, its length less one.
 #include <hip/hip_runtime.h>
@@ -36,6 +38,7 @@
 
 #include "pf_internal.h"
 #include "pf_matter_core.h"
+#include "pf_matter_slabs_core.h"
 
 #define MTHIP(task, who, call)                                                                                         \
   do {                                                                                                                 \
@@ -58,7 +61,9 @@ typedef unsigned long long u64;
 enum { MC_DEPOSITED = 0, MC_NONFINITE, MC_OUTSIDE, MC_EMPTY, MC_MAX, MC_SUMHI, MC_SUMLO, MC_NONFIN_MODES, MC_COUNT };
 #define MC_WORDS ((size_t)PF_MATTER_SLOTS * MC_COUNT)
 
-struct MatterCols { const void *vel12; size_t ncell; int n, nxl, x0, kmax, use_w; double w[4]; };
+// the particles are those of the slab [x0, x0 + nxl); the grid holds the wn planes w0, w0 + 1, ... (mod n) of the box -- the slab itself
+// with one rank, the slab and its ghost planes or the whole box in pf_matter_power_slabs (pf_matter_slabs_core.h)
+struct MatterCols { const void *vel12; size_t ncell; int n, nxl, x0, w0, wn, kmax, use_w; double w[4]; };
 
 __device__ __forceinline__ void matter_add(u64 *p, u64 v) {
   if (v) (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -99,8 +104,8 @@ __global__ void __launch_bounds__(PF_MATTER_BLOCK) k_matter_deposit(MatterCols c
     cls = pf_matter_class<T>(pos, c.n);
     if (cls == 0) {
       if (NGP) {
-        const int lx = pf_matter_ngp_axis<T>(pos[0], c.n) - c.x0;
-        if (lx >= 0 && lx < c.nxl)
+        const int lx = pf_matter_window_plane(pf_matter_ngp_axis<T>(pos[0], c.n), c.w0, c.wn, c.n);
+        if (lx >= 0)
           matter_add(grid + ((size_t)lx * n + (size_t)pf_matter_ngp_axis<T>(pos[1], c.n)) * n + (size_t)pf_matter_ngp_axis<T>(pos[2], c.n), PF_MATTER_ONE);
       } else {
         int cell[3][2];
@@ -109,8 +114,8 @@ __global__ void __launch_bounds__(PF_MATTER_BLOCK) k_matter_deposit(MatterCols c
         for (int j = 0; j < 3; j++) pf_matter_cic_axis<T>(pos[j], c.n, cell[j], wt[j]);
 #pragma unroll
         for (int a = 0; a < 2; a++) {
-          const int lx = cell[0][a] - c.x0;
-          if (lx < 0 || lx >= c.nxl || !wt[0][a]) continue;
+          const int lx = pf_matter_window_plane(cell[0][a], c.w0, c.wn, c.n);
+          if (lx < 0 || !wt[0][a]) continue;
 #pragma unroll
           for (int b = 0; b < 2; b++) {
             const u64 wxy = (u64)wt[0][a] * wt[1][b];
@@ -134,7 +139,7 @@ __global__ void __launch_bounds__(PF_MATTER_BLOCK) k_matter_deposit(MatterCols c
 // grid; the tile leaves with one global add per touched cell.  Integer adds in both places: the grid is that of the plain form, bit
 // for bit.  Needs n a multiple of 16 and nxl a multiple of 4 (matter_deposit falls back to the plain form otherwise).
 // Indices: a tile slot is used only after tx < TX, ty < TY, tz < TZ were checked; the flush maps a slot back through a
-// non-negative remainder by n, so its cell is in [0, n)^3, and the plane is deposited only inside the slab, as in the plain form.
+// non-negative remainder by n, so its cell is in [0, n)^3, and the plane is deposited only inside the window, as in the plain form.
 #define PF_ML_BX 4
 #define PF_ML_BY 4
 #define PF_ML_BZ 16
@@ -147,13 +152,13 @@ __global__ void __launch_bounds__(PF_MATTER_BLOCK) k_matter_deposit(MatterCols c
 __device__ __forceinline__ int matter_mod(int a, int n) { const int r = a % n; return r < 0 ? r + n : r; }
 
 struct MatterTile {
-  u64 *tile, *grid; const int *base; int n, nxl, x0;
+  u64 *tile, *grid; const int *base; int n, w0, wn;
   __device__ __forceinline__ void add(int cx, int cy, int cz, u64 w) const {
     if (!w) return;
     const int tx = matter_mod(cx - base[0], n), ty = matter_mod(cy - base[1], n), tz = matter_mod(cz - base[2], n);
     if (tx < PF_ML_TX && ty < PF_ML_TY && tz < PF_ML_TZ) { atomicAdd(&tile[(tx * PF_ML_TY + ty) * PF_ML_TZ + tz], w); return; }
-    const int lx = cx - x0;
-    if (lx >= 0 && lx < nxl) matter_add(grid + ((size_t)lx * n + (size_t)cy) * n + (size_t)cz, w);
+    const int lx = pf_matter_window_plane(cx, w0, wn, n);
+    if (lx >= 0) matter_add(grid + ((size_t)lx * n + (size_t)cy) * n + (size_t)cz, w);
   }
 };
 
@@ -196,7 +201,7 @@ __global__ void __launch_bounds__(PF_MATTER_BLOCK) k_matter_deposit_lds(MatterCo
     base[t] = org[t] + (int)floorf(m / (float)PF_MATTER_BLOCK + 0.5f) - PF_ML_M;   // |m / 256| < 1e6: no overflow
   }
   __syncthreads();
-  const MatterTile mt = {tile, grid, base, c.n, c.nxl, c.x0};
+  const MatterTile mt = {tile, grid, base, c.n, c.w0, c.wn};
   const int cls = pf_matter_class<T>(pos, c.n);
   if (cls == 0) {
     if (NGP) mt.add(pf_matter_ngp_axis<T>(pos[0], c.n), pf_matter_ngp_axis<T>(pos[1], c.n), pf_matter_ngp_axis<T>(pos[2], c.n), PF_MATTER_ONE);
@@ -220,8 +225,8 @@ __global__ void __launch_bounds__(PF_MATTER_BLOCK) k_matter_deposit_lds(MatterCo
     const u64 v = tile[k];
     if (!v) continue;
     const int tz = k % PF_ML_TZ, ty = k / PF_ML_TZ % PF_ML_TY, tx = k / (PF_ML_TZ * PF_ML_TY);
-    const int lx = matter_mod(base[0] + tx, c.n) - c.x0;
-    if (lx >= 0 && lx < c.nxl) matter_add(grid + ((size_t)lx * n + (size_t)matter_mod(base[1] + ty, c.n)) * n + (size_t)matter_mod(base[2] + tz, c.n), v);
+    const int lx = pf_matter_window_plane(matter_mod(base[0] + tx, c.n), c.w0, c.wn, c.n);
+    if (lx >= 0) matter_add(grid + ((size_t)lx * n + (size_t)matter_mod(base[1] + ty, c.n)) * n + (size_t)matter_mod(base[2] + tz, c.n), v);
   }
   u64 *slot = counters + (size_t)(blockIdx.x % PF_MATTER_SLOTS) * MC_COUNT;
   matter_count(cls == 0, slot + MC_DEPOSITED);
@@ -259,6 +264,69 @@ __global__ void __launch_bounds__(PF_MATTER_BLOCK) k_matter_contrast(const u64 *
     matter_max(slot + MC_MAX, mx);
     matter_add(slot + MC_EMPTY, empty); matter_add(slot + MC_SUMHI, hi); matter_add(slot + MC_SUMLO, lo);
   }
+}
+
+// ---- the slab form (pf_matter_power_slabs): how far the particles of this slab reach, and the fold of what the other ranks sent ----
+// reach: [PF_MATTER_SLOTS][2] words, cleared by the caller: the largest Hlo and Hhi (pf_matter_slabs_core.h) of the workgroups of a
+// slot.  One particle per lane as in k_matter_deposit, the four x columns alone (contiguous loads of a wave); a maximum per wave by
+// shuffles, per workgroup through LDS, then one atomic per workgroup and side -- and none where the slot already holds as much.
+// Indices: i < ncell; a slot is below PF_MATTER_SLOTS
+template <class T, int NGP>
+__global__ void __launch_bounds__(PF_MATTER_BLOCK) k_matter_reach(MatterCols c, u64 *reach) {
+  __shared__ int part[2][PF_MATTER_BLOCK / 64];
+  const size_t i = (size_t)blockIdx.x * PF_MATTER_BLOCK + threadIdx.x;
+  int lo = 0, hi = 0;
+  if (i < c.ncell) {
+    const unsigned int n = (unsigned int)c.n;
+    const int q0 = c.x0 + (int)(i / n / n);
+    const T *col = (const T *)c.vel12;
+    const double *w = c.use_w ? c.w : nullptr;
+    T v[4];
+#pragma unroll
+    for (int o = 0; o < 4; o++) v[o] = 3 * o < c.kmax ? pf_matter_column<T>(col[(size_t)(3 * o) * c.ncell + i], w, o) : (T)0;
+    int smin, smax;
+    if (pf_matter_reach<T>(pf_matter_pos<T>(q0, c.n, v[0], v[1], v[2], v[3]), q0, c.n, NGP, &smin, &smax)) {
+      lo = smin < 0 ? -smin : 0; hi = smax > 0 ? smax : 0;
+    }
+  }
+  for (int off = warpSize / 2; off; off >>= 1) {
+    const int a = __shfl_down(lo, off), b = __shfl_down(hi, off);
+    lo = a > lo ? a : lo; hi = b > hi ? b : hi;
+  }
+  if ((threadIdx.x & (warpSize - 1)) == 0) { part[0][threadIdx.x / warpSize] = lo; part[1][threadIdx.x / warpSize] = hi; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    int m = 0;
+    for (int k = 0; k < PF_MATTER_BLOCK / warpSize; k++) m = part[threadIdx.x][k] > m ? part[threadIdx.x][k] : m;
+    matter_max(reach + (size_t)(blockIdx.x % PF_MATTER_SLOTS) * 2 + threadIdx.x, (u64)m);
+  }
+}
+
+// own[l][..] += every received plane whose target is local plane l = blockIdx.y: sources first[l] .. first[l + 1] - 1 of `src`, each
+// the index of a plane of `recv` (peer * B + slot).  A thread owns its two words of the plane: plain 16-byte loads and one store,
+// 64-bit integer adds, no atomics.  pairs = n^2 / 2 (n is even).  Indices: l < nxl by the launch, a source below P B by the table,
+// i < pairs
+__global__ void __launch_bounds__(PF_MATTER_BLOCK) k_matter_fold(ulonglong2 *own, const ulonglong2 *recv, const int *first, const int *src, size_t pairs) {
+  const int l = blockIdx.y, k0 = first[l], k1 = first[l + 1];
+  if (k0 == k1) return;
+  for (size_t i = (size_t)blockIdx.x * PF_MATTER_BLOCK + threadIdx.x; i < pairs; i += (size_t)gridDim.x * PF_MATTER_BLOCK) {
+    ulonglong2 v = own[(size_t)l * pairs + i];
+    for (int k = k0; k < k1; k++) {
+      const ulonglong2 a = recv[(size_t)src[k] * pairs + i];
+      v.x += a.x; v.y += a.y;
+    }
+    own[(size_t)l * pairs + i] = v;
+  }
+}
+
+// out[i] = the largest of slots[p][i], p < P: the maximum over the ranks of `count` words, after the sum over the ranks of vectors in
+// which every rank filled its own slot alone
+__global__ void __launch_bounds__(PF_MATTER_BLOCK) k_matter_slot_max(const u64 *slots, int P, int count, u64 *out) {
+  const int i = blockIdx.x * PF_MATTER_BLOCK + threadIdx.x;
+  if (i >= count) return;
+  u64 m = 0;
+  for (int p = 0; p < P; p++) { const u64 v = slots[(size_t)p * count + i]; m = v > m ? v : m; }
+  out[i] = m;
 }
 
 // ------------------------------------------------------------------------------------------------------------ shell sums ----
@@ -435,9 +503,9 @@ static int matter_check_common(const char *who, int task, int flags, const doubl
   return 0;
 }
 
-// grid (cleared here) += the particles of the slab; counters: MC_WORDS words, cleared by the caller
+// grid (the wn planes of the window, cleared here) += the particles of the slab; counters: MC_WORDS words, cleared by the caller
 static int matter_deposit(const char *who, int task, int pb, const MatterCols &c, int flags, u64 *grid, u64 *counters, hipStream_t st) {
-  MTHIP(task, who, hipMemsetAsync(grid, 0, c.ncell * 8, st));
+  MTHIP(task, who, hipMemsetAsync(grid, 0, (size_t)c.wn * c.n * c.n * 8, st));
   const size_t nblk = (c.ncell + PF_MATTER_BLOCK - 1) / PF_MATTER_BLOCK;
   if (nblk > 0x7fffffffull) return pf_fail(task, "%s: %zu cells are more than one launch takes (internal error)", who, c.ncell);
   const dim3 gr((unsigned int)nblk), bl(PF_MATTER_BLOCK);
@@ -466,15 +534,18 @@ static int matter_contrast(const char *who, int task, int fb, const u64 *grid, s
   return 0;
 }
 static void matter_cols(MatterCols *c, const void *vel12, size_t ncell, int n, int nxl, int x0, int kmax, const double *weight) {
-  c->vel12 = vel12; c->ncell = ncell; c->n = n; c->nxl = nxl; c->x0 = x0; c->kmax = kmax; c->use_w = weight != nullptr;
+  c->vel12 = vel12; c->ncell = ncell; c->n = n; c->nxl = nxl; c->x0 = x0; c->w0 = x0; c->wn = nxl; c->kmax = kmax; c->use_w = weight != nullptr;
   for (int k = 0; k < 4; k++) c->w[k] = weight ? weight[k] : 1.0;
 }
 
 // words of the shell tables: smax [3 nb], nm [nb], k2 [nb], pl [12 nb]; then out [2 nb] doubles and the deconvolution table [n/2 + 1]
 static size_t matter_shell_words(int n) { return (size_t)19 * pf_power_nbins(n) + (size_t)(n / 2 + 1); }
 // the rows y0 .. y0 + nyl - 1 of two spectra on the device -> this slab's sums in the tables at `words` (matter_shell_words(n) of them, not yet cleared).  Nothing is synchronised
+// coll (more than one rank, collective): the sums of the box on every rank -- the maxima of the scans over the ranks through `slots`
+// (P x 3 nb words), then the integer tables summed over the ranks; every all-reduce runs on the context's stream, which is st
+struct MatterColl { pf_ctx *c; int P, rank; u64 *slots; };
 static int matter_shells(const char *who, int task, int fb, const void *spec_m, const void *spec_lin, int n, int y0, int nyl, long long pitch, int flags, u64 *words,
-                         u64 *counters, MatterTabs *g, hipStream_t st) {
+                         u64 *counters, MatterTabs *g, hipStream_t st, const MatterColl *coll = nullptr) {
   const int nb = pf_power_nbins(n), nzh = n / 2 + 1;
   MatterView v;
   v.m = spec_m; v.lin = spec_lin; v.C = nullptr; v.n = n; v.nyl = nyl; v.y0 = y0; v.pitch = pitch;
@@ -504,15 +575,29 @@ static int matter_shells(const char *who, int task, int fb, const void *spec_m, 
     if (fb == 8) hipLaunchKernelGGL((k_matter_scan<double, true>), gr, bl, lds_all, st, v, 0, nb, *g, counters);
     else hipLaunchKernelGGL((k_matter_scan<float, true>), gr, bl, lds_all, st, v, 0, nb, *g, counters);
   }
-  for (int which = 0; which < (spec_lin ? 3 : 1); which++) {
-    if (!fused) {
-      if (fb == 8) hipLaunchKernelGGL((k_matter_scan<double, false>), gr, bl, lds, st, v, which, nb, *g, counters);
-      else hipLaunchKernelGGL((k_matter_scan<float, false>), gr, bl, lds, st, v, which, nb, *g, counters);
+  // more than one rank: every scan first, then the maxima of the box, so that every limb of every rank is formed under the box's exponent
+  for (int pass = coll ? 0 : 1; pass < 2; pass++) {
+    for (int which = 0; which < (spec_lin ? 3 : 1); which++) {
+      if (!fused && (!coll || pass == 0)) {
+        if (fb == 8) hipLaunchKernelGGL((k_matter_scan<double, false>), gr, bl, lds, st, v, which, nb, *g, counters);
+        else hipLaunchKernelGGL((k_matter_scan<float, false>), gr, bl, lds, st, v, which, nb, *g, counters);
+      }
+      if (pass == 1) {
+        if (fb == 8) hipLaunchKernelGGL((k_matter_acc<double>), gr, bl, lds, st, v, which, nb, *g);
+        else hipLaunchKernelGGL((k_matter_acc<float>), gr, bl, lds, st, v, which, nb, *g);
+      }
+      if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
     }
-    if (fb == 8) hipLaunchKernelGGL((k_matter_acc<double>), gr, bl, lds, st, v, which, nb, *g);
-    else hipLaunchKernelGGL((k_matter_acc<float>), gr, bl, lds, st, v, which, nb, *g);
-    if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+    if (coll && pass == 0) {
+      const size_t cnt = (size_t)3 * nb;
+      MTHIP(task, who, hipMemsetAsync(coll->slots, 0, (size_t)coll->P * cnt * 8, st));
+      MTHIP(task, who, hipMemcpyAsync(coll->slots + (size_t)coll->rank * cnt, g->smax, cnt * 8, hipMemcpyDeviceToDevice, st));
+      if (pf_ctx_allreduce(coll->c, coll->slots, (size_t)coll->P * cnt, 1)) return 1;
+      hipLaunchKernelGGL(k_matter_slot_max, dim3((unsigned int)((cnt + PF_MATTER_BLOCK - 1) / PF_MATTER_BLOCK)), bl, 0, st, coll->slots, coll->P, (int)cnt, g->smax);
+      if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+    }
   }
+  if (coll && pf_ctx_allreduce(coll->c, g->nm, (size_t)14 * nb, 1)) return 1;   // nm, k2 and the limbs pl lie one behind the other
   matter_last_scans = fused ? 1 : spec_lin ? 3 : 1;
   const double n3 = (double)n * (double)n * (double)n;
   hipLaunchKernelGGL(k_matter_final, dim3((unsigned int)((nb + PF_MATTER_BLOCK - 1) / PF_MATTER_BLOCK)), dim3(PF_MATTER_BLOCK), 0, st, nb, n3 * n3, *g);
@@ -520,9 +605,20 @@ static int matter_shells(const char *who, int task, int fb, const void *spec_m, 
   return 0;
 }
 
-// the counters and, with g, the shell sums -> the caller's arrays
+// a few words of the host summed over the ranks of the context, through `dev` (as many words on the device) on the context's stream
+static int matter_agree(const char *who, int task, pf_ctx *c, u64 *dev, std::vector<u64> &a, hipStream_t st) {
+  MTHIP(task, who, hipMemcpyAsync(dev, a.data(), a.size() * 8, hipMemcpyHostToDevice, st));
+  MTHIP(task, who, hipStreamSynchronize(st));
+  if (pf_ctx_allreduce(c, dev, a.size(), 1)) return 1;
+  MTHIP(task, who, hipMemcpyAsync(a.data(), dev, a.size() * 8, hipMemcpyDeviceToHost, st));
+  MTHIP(task, who, hipStreamSynchronize(st));
+  return 0;
+}
+
+// the counters and, with g, the shell sums -> the caller's arrays; coll: the counters of the box (collective, through `agree`:
+// MC_COUNT + P words on the device)
 static int matter_fetch(const char *who, int task, int n, const u64 *counters, const MatterTabs *g, u64 modes, u64 *nmodes, u64 *k2sum, double *power, double *cross,
-                        pf_matter_info *info, hipStream_t st) {
+                        pf_matter_info *info, hipStream_t st, const MatterColl *coll = nullptr, u64 *agree = nullptr) {
   std::vector<u64> slots((size_t)PF_MATTER_SLOTS * MC_COUNT);
   MTHIP(task, who, hipMemcpyAsync(slots.data(), counters, slots.size() * 8, hipMemcpyDeviceToHost, st));
   if (g) {
@@ -542,6 +638,14 @@ static int matter_fetch(const char *who, int task, int n, const u64 *counters, c
       const u64 v = slots[(size_t)k * MC_COUNT + i];
       if (i == MC_MAX) hc[i] = v > hc[i] ? v : hc[i]; else hc[i] += v;
     }
+  if (coll) {   // the box's: sums over the ranks, and the largest cell through a slot per rank
+    std::vector<u64> a((size_t)MC_COUNT + coll->P, 0);
+    for (int i = 0; i < MC_COUNT; i++) a[i] = i == MC_MAX ? 0 : hc[i];
+    a[(size_t)MC_COUNT + coll->rank] = hc[MC_MAX];
+    if (matter_agree(who, task, coll->c, agree, a, st)) return 1;
+    for (int i = 0; i < MC_COUNT; i++) hc[i] = a[i];
+    for (int p = 0; p < coll->P; p++) hc[MC_MAX] = a[(size_t)MC_COUNT + p] > hc[MC_MAX] ? a[(size_t)MC_COUNT + p] : hc[MC_MAX];
+  }
   info->deposited = hc[MC_DEPOSITED]; info->nonfinite = hc[MC_NONFINITE]; info->outside = hc[MC_OUTSIDE]; info->empty_cells = hc[MC_EMPTY];
   info->max_cell = hc[MC_MAX]; info->sum_hi32 = hc[MC_SUMHI]; info->sum_lo32 = hc[MC_SUMLO]; info->modes = modes; info->nonfinite_modes = hc[MC_NONFIN_MODES];
   return 0;
@@ -664,4 +768,237 @@ extern "C" int pf_debug_matter_shells(int field_bytes, int n, int y0, int nyl, c
   const int phases[4] = {3, 3, 3, 3};
   timer.end(phases);
   return matter_fetch(who, 0, n, s.words, &g, (u64)nyl * n * n, nmodes, k2sum, power, cross, info, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------------------ slabs ----
+// pf_matter_power_slabs: the call above on any number of ranks.  The particles of a slab leave it: every rank finds how far
+// (k_matter_reach), the ranks agree on the largest reach both ways, every rank deposits into a window of its slab and that many
+// ghost planes (or the whole box), the ghost planes travel to their owners in one all-to-all of the context and are added there
+// (k_matter_fold).  Integer adds on every rank: the grid is the one-rank grid.  The plan is pf_matter_slabs_core.h's.
+static thread_local u64 matter_last_exchange[6] = {0, 0, 0, 0, 0, 0};
+extern "C" int pf_debug_matter_exchange(unsigned long long out[6]) {
+  if (!out) return 1;
+  for (int i = 0; i < 6; i++) out[i] = matter_last_exchange[i];
+  return 0;
+}
+
+struct SlabBufs { u64 *win, *send, *recv, *words; int *tab; void *cols; };
+struct SlabGuard {
+  SlabBufs *b;
+  ~SlabGuard() { hipFree(b->win); hipFree(b->send); hipFree(b->recv); hipFree(b->words); hipFree(b->tab); hipFree(b->cols); memset(b, 0, sizeof(*b)); }
+};
+// the words of a call beside the window and the blocks: the counters, the shell tables (shells: a whole call), the reach slots, the
+// few words the ranks agree on, and the slots of the scans' maxima
+struct SlabWords { size_t shell, reach, agree, slots, total; };
+static SlabWords slab_words(int n, int P, bool shells) {
+  SlabWords w;
+  const size_t a = (size_t)2 * P + 1, b = (size_t)MC_COUNT + P;
+  w.shell = MC_WORDS; w.reach = w.shell + (shells ? matter_shell_words(n) : 0); w.agree = w.reach + (size_t)2 * PF_MATTER_SLOTS;
+  w.slots = w.agree + (a > b ? a : b);
+  w.total = w.slots + (shells && P > 1 ? (size_t)P * 3 * pf_power_nbins(n) : 0);
+  return w;
+}
+
+// a rank that refuses on its own (its message stands in pf_last_error) still meets the others in the first all-reduce, with its flag
+static int slab_refuse(const char *who, pf_ctx *c, const PfSpecView &sv) {
+  if (sv.P == 1) return 1;
+  u64 *dev = nullptr;
+  const size_t cnt = (size_t)2 * sv.P + 1;
+  if (hipMalloc((void **)&dev, cnt * 8) != hipSuccess) { (void)hipGetLastError(); return 1; }
+  std::vector<u64> a(cnt, 0);
+  a[cnt - 1] = 1;
+  (void)matter_agree(who, sv.rank, c, dev, a, sv.stream);   // (a successful all-reduce leaves the message as it is)
+  hipFree(dev);
+  return 1;
+}
+
+struct SlabPlan { int hlo, hhi, form, w0, wn, B, own; };
+
+// the window of this rank's slab after deposit, exchange and fold: b->win, the rank's own planes from plane pl->own on.  cols: the
+// particle slab (its window is set here); b->words is allocated (slab_words) and its counters are cleared.  Collective
+static int slab_grid(const char *who, pf_ctx *c, const PfSpecView &sv, int pb, MatterCols cols, int flags, const SlabWords &sw, SlabBufs *b, SlabPlan *pl) {
+  const int task = sv.rank, n = cols.n, P = sv.P, nxl = cols.nxl;
+  hipStream_t st = sv.stream;
+  u64 *reach = b->words + sw.reach, *agree = b->words + sw.agree;
+  const bool ngp = (flags & PF_MATTER_NGP) != 0;
+  // 1. the reach of this slab, then of every slab
+  MTHIP(task, who, hipMemsetAsync(reach, 0, (size_t)2 * PF_MATTER_SLOTS * 8, st));
+  const size_t nblk = (cols.ncell + PF_MATTER_BLOCK - 1) / PF_MATTER_BLOCK;
+  if (nblk > 0x7fffffffull) return pf_fail(task, "%s: %zu cells are more than one launch takes (internal error)", who, cols.ncell);
+  const dim3 gr((unsigned int)nblk), bl(PF_MATTER_BLOCK);
+  if (pb == 8) { if (ngp) hipLaunchKernelGGL((k_matter_reach<double, 1>), gr, bl, 0, st, cols, reach); else hipLaunchKernelGGL((k_matter_reach<double, 0>), gr, bl, 0, st, cols, reach); }
+  else { if (ngp) hipLaunchKernelGGL((k_matter_reach<float, 1>), gr, bl, 0, st, cols, reach); else hipLaunchKernelGGL((k_matter_reach<float, 0>), gr, bl, 0, st, cols, reach); }
+  if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+  std::vector<u64> hr((size_t)2 * PF_MATTER_SLOTS);
+  MTHIP(task, who, hipMemcpyAsync(hr.data(), reach, hr.size() * 8, hipMemcpyDeviceToHost, st));
+  MTHIP(task, who, hipStreamSynchronize(st));
+  u64 hlo = 0, hhi = 0;
+  for (int k = 0; k < PF_MATTER_SLOTS; k++) { hlo = hr[2 * k] > hlo ? hr[2 * k] : hlo; hhi = hr[2 * k + 1] > hhi ? hr[2 * k + 1] : hhi; }
+  if (P > 1) {
+    std::vector<u64> a((size_t)2 * P + 1, 0);
+    a[sv.rank] = hlo; a[(size_t)P + sv.rank] = hhi;
+    if (matter_agree(who, task, c, agree, a, st)) return 1;
+    if (a[(size_t)2 * P]) return pf_fail(task, "%s: refused on another rank of the context", who);
+    for (int p = 0; p < P; p++) { hlo = a[p] > hlo ? a[p] : hlo; hhi = a[(size_t)P + p] > hhi ? a[(size_t)P + p] : hhi; }
+  }
+  pl->hlo = (int)hlo; pl->hhi = (int)hhi;   // (each at most n / 2)
+  // 2. the plan, the window and the blocks
+  pl->form = pf_matter_exchange_form(n, P, pl->hlo, pl->hhi);
+  pf_matter_window(n, nxl, cols.x0, pl->hlo, pl->hhi, &pl->w0, &pl->wn);
+  pl->own = pf_matter_window_plane(cols.x0, pl->w0, pl->wn, n);
+  pl->B = pl->form ? pf_matter_block_planes(n, P, pl->hlo, pl->hhi) : 0;
+  const size_t plane = (size_t)n * n, block = (size_t)pl->B * plane;
+  const size_t bytes = ((size_t)pl->wn + 2 * (size_t)P * pl->B) * plane * 8;
+  // the fold's table: first[nxl + 1], then the sources by target plane
+  std::vector<int> first(nxl + 1, 0), src, list(nxl);
+  if (pl->form) {
+    std::vector<std::vector<int>> by(nxl);
+    for (int p = 0; p < P; p++) {
+      if (p == sv.rank) continue;
+      const int len = pf_matter_block_list(n, P, pl->hlo, pl->hhi, p, sv.rank, list.data());
+      for (int j = 0; j < len; j++) by[list[j]].push_back(p * pl->B + j);
+    }
+    for (int l = 0; l < nxl; l++) { first[l + 1] = first[l] + (int)by[l].size(); src.insert(src.end(), by[l].begin(), by[l].end()); }
+  }
+  bool failed = hipMalloc((void **)&b->win, (size_t)pl->wn * plane * 8) != hipSuccess;
+  if (pl->form && !failed)
+    failed = hipMalloc((void **)&b->send, (size_t)P * block * 8) != hipSuccess || hipMalloc((void **)&b->recv, (size_t)P * block * 8) != hipSuccess ||
+             hipMalloc((void **)&b->tab, (first.size() + src.size() + 1) * sizeof(int)) != hipSuccess;
+  if (failed) { (void)hipGetLastError(); pf_fail(task, "%s: cannot allocate %zu bytes of scratch on the device", who, bytes + sw.total * 8); }
+  if (P > 1) {
+    std::vector<u64> a(1, failed ? 1 : 0);
+    if (matter_agree(who, task, c, agree, a, st)) return 1;
+    if (a[0] && !failed) return pf_fail(task, "%s: another rank of the context cannot allocate its scratch", who);
+  }
+  if (failed) return 1;
+  matter_last_exchange[0] = (u64)pl->form; matter_last_exchange[1] = (u64)pl->hlo; matter_last_exchange[2] = (u64)pl->hhi;
+  matter_last_exchange[3] = (u64)pl->wn; matter_last_exchange[4] = (u64)pl->B; matter_last_exchange[5] = (u64)block * 8;
+  // 3. deposit, and what leaves and arrives
+  cols.w0 = pl->w0; cols.wn = pl->wn;
+  if (matter_deposit(who, task, pb, cols, flags, b->win, b->words, st)) return 1;
+  if (!pl->form) return 0;
+  MTHIP(task, who, hipMemcpyAsync(b->tab, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  if (!src.empty()) MTHIP(task, who, hipMemcpyAsync(b->tab + first.size(), src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  MTHIP(task, who, hipStreamSynchronize(st));   // (pageable memory: the tables may go once the copies have left them)
+  for (int q = 0; q < P; q++) {
+    if (q == sv.rank) continue;
+    const int len = pf_matter_block_list(n, P, pl->hlo, pl->hhi, sv.rank, q, list.data());
+    for (int j = 0; j < len;) {   // slots j .. e - 1: planes that follow each other in the window too, one copy
+      const int wp = pf_matter_window_plane(q * nxl + list[j], pl->w0, pl->wn, n);
+      int e = j + 1;
+      while (e < len && pf_matter_window_plane(q * nxl + list[e], pl->w0, pl->wn, n) == wp + (e - j)) e++;
+      MTHIP(task, who, hipMemcpyAsync(b->send + ((size_t)q * pl->B + j) * plane, b->win + (size_t)wp * plane, (size_t)(e - j) * plane * 8, hipMemcpyDeviceToDevice, st));
+      j = e;
+    }
+  }
+  if (pf_ctx_alltoall(c, b->send, b->recv, block * 8)) return 1;
+  if (!src.empty()) {
+    const size_t pairs = plane / 2, want = (pairs + PF_MATTER_BLOCK - 1) / PF_MATTER_BLOCK;
+    const dim3 gf((unsigned int)(want < 4096 ? want : 4096), (unsigned int)nxl);
+    hipLaunchKernelGGL(k_matter_fold, gf, bl, 0, st, (ulonglong2 *)(b->win + (size_t)pl->own * plane), (const ulonglong2 *)b->recv, b->tab, b->tab + first.size(), pairs);
+    if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+  }
+  return 0;
+}
+
+// what both entry points check before anything is launched -> 1 with the message set
+static int slab_check(const char *who, pf_ctx *c, const PfSpecView &sv, int flags, const double *weight, const pf_matter_info *info) {
+  if (matter_check_common(who, sv.rank, flags, weight, info)) return 1;
+  if (sv.P > 1 && (sv.n & 1)) return pf_fail(sv.rank, "%s: a grid of %d on %d ranks (even sizes only: the fold adds two words at a time)", who, sv.n, sv.P);
+  return 0;
+}
+
+extern "C" int pf_matter_power_slabs(pf_ctx *c, int flags, const double *weight, unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross,
+                                     double *density_host, pf_matter_info *info) {
+  const char *who = "pf_matter_power_slabs";
+  if (!c) return pf_fail(0, "%s: null argument", who);
+  PfSpecView sv;
+  pf_ctx_spec_geometry(c, &sv);
+  if (sv.P > 1 && !pf_ctx_exchange_installed(c)) return pf_fail(sv.rank, "%s: no exchange installed for %d ranks (pf_set_exchange and pf_set_allreduce / pf_init_rccl)", who, sv.P);
+  PfCtxView cv;
+  pf_ctx_view(c, &cv);
+  // every check a rank makes on its own; what it finds it tells the others before anything is launched
+  int bad = 0;
+  if (!nmodes || !k2sum || !power) bad = pf_fail(sv.rank, "%s: null argument", who);
+  if (!bad) bad = slab_check(who, c, sv, flags, weight, info);
+  if (!bad && cross) bad = pf_ctx_spec_view(c, who, 0, &sv);   // "density not set" (which = 0: nothing is launched)
+  if (!bad && !cv.products_init) bad = pf_fail(sv.rank, "%s: products not computed", who);
+  SlabBufs b;
+  memset(&b, 0, sizeof(b));
+  SlabGuard guard{&b};
+  const SlabWords sw = slab_words(sv.n, sv.P, true);
+  if (!bad && hipMalloc((void **)&b.words, sw.total * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    bad = pf_fail(sv.rank, "%s: cannot allocate %zu bytes of scratch on the device", who, sw.total * 8);
+  }
+  if (bad) return slab_refuse(who, c, sv);
+  PfMatterCtx mc;
+  pf_ctx_matter_view(c, &mc);
+  if (pf_ctx_velocities_ready(c)) return 1;
+  u64 *counters = b.words;
+  MTHIP(sv.rank, who, hipMemsetAsync(counters, 0, MC_WORDS * 8, sv.stream));
+  MatterTimer timer(sv.stream);
+  MatterCols cols;
+  matter_cols(&cols, cv.vel12, cv.ncell, cv.n, cv.nxl, mc.x0, mc.lpt_order >= 3 ? 12 : mc.lpt_order == 2 ? 6 : 3, weight);
+  SlabPlan pl;
+  if (slab_grid(who, c, sv, cv.pb, cols, flags, sw, &b, &pl)) return 1;
+  timer.mark();
+  if (matter_contrast(who, sv.rank, sv.fb, b.win + (size_t)pl.own * cv.n * cv.n, cv.ncell, cv.n, mc.rpitch, mc.field, counters, sv.stream)) return 1;
+  timer.mark();
+  int phases[5] = {0, 1, 2, 3, 3}, np = 2;
+  if (density_host) {
+    if (pf_ctx_matter_export(c, density_host)) return 1;
+    timer.mark();
+    phases[np++] = -1;
+  }
+  if (pf_ctx_matter_forward(c)) return 1;
+  timer.mark();
+  phases[np++] = 2;
+  MatterTabs g;
+  const MatterColl coll = {c, sv.P, sv.rank, b.words + sw.slots};
+  const MatterColl *cp = sv.P > 1 ? &coll : nullptr;
+  if (matter_shells(who, sv.rank, sv.fb, mc.field, cross ? sv.spec : nullptr, sv.n, sv.y0, sv.nyl, sv.nzp, flags, b.words + sw.shell, counters, &g, sv.stream, cp)) return 1;
+  timer.mark();
+  phases[np++] = 3;
+  timer.end(phases);
+  return matter_fetch(who, sv.rank, sv.n, counters, &g, (u64)sv.n * sv.n * sv.n, nmodes, k2sum, power, cross, info, sv.stream, cp, b.words + sw.agree);
+}
+
+extern "C" int pf_debug_matter_slabs(pf_ctx *c, const void *vel12_slab_host, int flags, const double *weight, unsigned long long *grid_slab_host, pf_matter_info *info) {
+  const char *who = "pf_debug_matter_slabs";
+  if (!c) return pf_fail(0, "%s: null argument", who);
+  PfSpecView sv;
+  pf_ctx_spec_geometry(c, &sv);
+  if (sv.P > 1 && !pf_ctx_exchange_installed(c)) return pf_fail(sv.rank, "%s: no exchange installed for %d ranks (pf_set_exchange and pf_set_allreduce / pf_init_rccl)", who, sv.P);
+  PfCtxView cv;
+  pf_ctx_view(c, &cv);
+  int bad = 0;
+  if (!vel12_slab_host || !grid_slab_host) bad = pf_fail(sv.rank, "%s: null argument", who);
+  if (!bad) bad = slab_check(who, c, sv, flags, weight, info);
+  SlabBufs b;
+  memset(&b, 0, sizeof(b));
+  SlabGuard guard{&b};
+  const SlabWords sw = slab_words(sv.n, sv.P, false);
+  const size_t col_bytes = 12 * cv.ncell * (size_t)cv.pb;
+  if (!bad && (hipMalloc((void **)&b.words, sw.total * 8) != hipSuccess || hipMalloc(&b.cols, col_bytes) != hipSuccess)) {
+    (void)hipGetLastError();
+    bad = pf_fail(sv.rank, "%s: cannot allocate %zu bytes of scratch on the device", who, sw.total * 8 + col_bytes);
+  }
+  if (bad) return slab_refuse(who, c, sv);
+  MTHIP(sv.rank, who, hipMemcpyAsync(b.cols, vel12_slab_host, col_bytes, hipMemcpyHostToDevice, sv.stream));
+  MTHIP(sv.rank, who, hipMemsetAsync(b.words, 0, MC_WORDS * 8, sv.stream));
+  MatterTimer timer(sv.stream);
+  MatterCols cols;
+  matter_cols(&cols, b.cols, cv.ncell, cv.n, cv.nxl, sv.rank * cv.nxl, 12, weight);
+  SlabPlan pl;
+  if (slab_grid(who, c, sv, cv.pb, cols, flags, sw, &b, &pl)) return 1;
+  timer.mark();
+  const u64 *own = b.win + (size_t)pl.own * cv.n * cv.n;
+  if (matter_contrast(who, sv.rank, 0, own, cv.ncell, cv.n, cv.n, nullptr, b.words, sv.stream)) return 1;
+  timer.mark();
+  const int phases[4] = {0, 1, 2, 3};
+  timer.end(phases);
+  MTHIP(sv.rank, who, hipMemcpyAsync(grid_slab_host, own, cv.ncell * 8, hipMemcpyDeviceToHost, sv.stream));
+  const MatterColl coll = {c, sv.P, sv.rank, nullptr};
+  return matter_fetch(who, sv.rank, sv.n, b.words, nullptr, 0, nullptr, nullptr, nullptr, nullptr, info, sv.stream, sv.P > 1 ? &coll : nullptr, b.words + sw.agree);
 }
