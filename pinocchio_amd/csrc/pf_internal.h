@@ -384,6 +384,23 @@ int pf_ctx_allreduce(pf_ctx *c, void *buf_dev, size_t count, int is_u64);   // t
 // the installed pf_alltoall_fn on the context's stream: block q of send_dev goes to rank q, block p of recv_dev comes from rank p
 int pf_ctx_alltoall(pf_ctx *c, const void *send_dev, void *recv_dev, size_t bytes_per_peer);
 int pf_ctx_exchange_installed(pf_ctx *c);   // one rank, or both an all-to-all and an all-reduce are installed
+// the staging of the taps on a caller's spectra (pf_debug_power_spectrum, pf_debug_matter_shells): after the refusals of field_bytes,
+// n, y0 and nyl, one or two ky-slabs [ky_local][kx][kz] of the host (b may be null) into `fields` fields in the production layout,
+// rows of nzp complex, and `words` 64-bit words of scratch beside them (0: none); *d starts zeroed and frees what it holds
+struct PfSpecStage { void *in, *spec[2]; unsigned long long *words; int nzp; ~PfSpecStage() { hipFree(in); hipFree(spec[0]); hipFree(words); } };
+int pf_stage_spectra(const char *who, int field_bytes, int n, int y0, int nyl, int fields, const double *a, const double *b, size_t words, PfSpecStage *d);
+// the shell sums of two resident spectra, |m|^2 and Re(m conj lin) (lin null: the first alone), of the rows y0 .. y0 + nyl - 1 ->
+// this slab's sums on the device, or with coll (collective) the box's on every rank: nm ([nb] nmodes, [nb] k2sum) and out ([nb]
+// power, [nb] cross).  words: pf_matter_shells_words(n, ranks of coll) of them, not yet cleared.  Nothing is synchronised
+struct PfShellSums { const unsigned long long *nm; const double *out; int scans; };   // scans: the scan launches (pf_debug_matter_form)
+size_t pf_matter_shells_words(int n, int P);
+int pf_matter_shells_device(const char *who, int task, int fb, const void *spec_m, const void *spec_lin, int n, int y0, int nyl, long long pitch, int flags,
+                            unsigned long long *words, unsigned long long *counters, pf_ctx *coll, PfShellSums *sums, hipStream_t st);
+// counters of a pf_matter call on the device: PF_MATTER_SLOTS copies of each, a workgroup adds to the copy of its index -- one counter for all
+// wavefronts of a 1024^3 call is 1.7e7 atomics on one address: the contrast pass took 778 ms that way and takes 8 (profiles/matter_notes.md);
+// the copies are summed (MC_MAX: reduced) on the host.  The scans of pf_matter_shells_device add to MC_NONFIN_MODES of `counters`
+#define PF_MATTER_SLOTS 1024
+enum { MC_DEPOSITED = 0, MC_NONFINITE, MC_OUTSIDE, MC_EMPTY, MC_MAX, MC_SUMHI, MC_SUMLO, MC_NONFIN_MODES, MC_COUNT };
 // ---- pf_matter.hip: the density of the displaced particles and its spectra; what it sees of a context beside the views above ----
 // field: the scratch field of the transform taps (real rows of rpitch reals, then its spectrum in the layout of PfSpecView; with more
 // than one rank that is receive field 0, the field pf_forward_transform uses there); x0: global x

@@ -1,5 +1,5 @@
-// pf_power.hip -- shell-averaged power and Gaussian-smoothed variances of a half-spectrum that lies on the device (include/pinfmax.h:
-// pf_power_spectrum, pf_debug_power_spectrum): two streaming reads of the rows of this rank's ky-slab, [kx][ky_local] rows of `pitch`
+// pf_power.hip -- every shell sum over spectra that lie on the device.  First the shell-averaged power and Gaussian-smoothed variances
+// of one half-spectrum (include/pinfmax.h: pf_power_spectrum, pf_debug_power_spectrum): two streaming reads of the rows of this rank's ky-slab, [kx][ky_local] rows of `pitch`
 // complex of which the first n/2 + 1 are modes; the padding behind them is never read.  The mode arithmetic is pf_power_core.h's.
 //
 // The walk of both kernels: workgroup g takes the rows [g rpw, (g + 1) rpw) one after the other; thread t owns the columns kz = t +
@@ -24,10 +24,22 @@
 // 1) exponentials) -- two multiplications per mode and radius in place of an exponential in each of the two passes.  Radii go in
 // batches of PF_POWER_NR per pair of launches (their registers); the shells ride with the first batch.
 //
+// Then the sums of two spectra, |m|^2 and Re(m conj lin) per shell, for pf_matter.hip (pf_matter_shells_device; the mode arithmetic is
+// pf_matter_core.h's) -- the same two passes and the same fixed point on the same helpers, with a walk of their own (matter_walk: a
+// thread at the columns kz = t, t + 256, ..., the root of every mode anew), not merged with the one above:
+//  k_matter_scan  three positive sums per shell (0 |m|^2, 1 the positive cross terms, 2 the negative ones): ONE scan takes the largest
+//                 term of every shell for all three, with nmodes, k2sum and the modes whose terms are not finite (five LDS tables;
+//                 where they do not fit, n above about 1800, a scan per sum).
+//  k_matter_acc   an accumulation per sum adds every term as three 32-bit limbs scaled to that maximum (LDS holds one sum's
+//                 counters, so every grid up to 2048 fits).  Four passes over the two spectra (profiles/matter_notes.md).
+//  k_matter_final limbs -> double, times 1 / N^6; cross = positive - negative, formed once.
+//  k_matter_slot_max  with more than one rank: the maxima of the scans over the ranks, before any limb is formed.
+//
 // Every index is in range by construction: a mode is read only in the workgroup's own rows (< rows), at a column kz <= n/2 < pitch;
 // a shell is below pf_power_nbins(n), which sized every table, since k2 <= 3 (n/2)^2; a radius index is below the batch's nr <=
 // PF_POWER_NR inside a kernel and below ns in HBM; the window tables are read at |kx|, |ky|, kz <= n/2, their row length less one;
-// the dynamic LDS is sized by nbins and PF_POWER_NR.
+// the dynamic LDS is sized by nbins and PF_POWER_NR; the deconvolution table of the two-spectrum passes is read at |kx|, |ky|, kz <=
+// n/2, its length less one, and a counter slot is blockIdx.x mod PF_MATTER_SLOTS of the MC_COUNT words each the caller allocated.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -37,7 +49,7 @@
 #include <vector>
 
 #include "pf_internal.h"
-#include "pf_power_core.h"
+#include "pf_matter_core.h"   // the two terms of a mode of two spectra; it includes pf_power_core.h
 
 #define PWHIP(task, who, call)                                                                                         \
   do {                                                                                                                 \
@@ -63,10 +75,16 @@ struct PowerBatch { int nr, r0, shells; const double *E; };
 // the tables in HBM, 64-bit words: one allocation, cleared before the scan
 struct PowerTabs { u64 *smax, *vmax, *nm, *k2, *nonfin, *pl, *vl; double *out; };
 
-template <class F> __device__ __forceinline__ double power_load(const PowerView &v, unsigned int row, unsigned int kz) {
-  const F *e = (const F *)v.spec + 2 * ((long long)row * v.pitch + kz);
-  if constexpr (sizeof(F) == 8) { const double2 x = *(const double2 *)e; return pf_power_term<double>(x.x, x.y); }
-  else { const float2 x = *(const float2 *)e; return pf_power_term<float>(x.x, x.y); }
+// one complex element of a spectrum, widened to double (exact), and its term
+template <class F> __device__ __forceinline__ void power_load(const void *spec, long long pitch, unsigned int row, unsigned int kz, double &re, double &im) {
+  const F *e = (const F *)spec + 2 * ((long long)row * pitch + kz);
+  if constexpr (sizeof(F) == 8) { const double2 x = *(const double2 *)e; re = x.x; im = x.y; }
+  else { const float2 x = *(const float2 *)e; re = (double)x.x; im = (double)x.y; }
+}
+template <class F> __device__ __forceinline__ double power_term_at(const PowerView &v, unsigned int row, unsigned int kz) {
+  double re, im;
+  power_load<F>(v.spec, v.pitch, row, kz, re, im);
+  return pf_power_term<double>(re, im);
 }
 
 // the rows of this workgroup and the (kx, ky_local) of the first
@@ -76,6 +94,12 @@ __device__ __forceinline__ void power_rows(const PowerView &v, unsigned int &r0,
   kx = r0 / (unsigned int)v.nyl; yl = r0 - kx * (unsigned int)v.nyl;
 }
 __device__ __forceinline__ unsigned int power_abs(int s) { return (unsigned int)(s < 0 ? -s : s); }
+// a maximum in LDS only grows: a term that is not above what a relaxed read saw needs no atomic
+__device__ __forceinline__ void power_max_lds(u64 *p, u64 v) {
+  if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) atomicMax(p, v);
+}
+// the scale exponent of a stored maximum, the bit pattern of a double (none: no positive term, nothing is added under it)
+__device__ __forceinline__ int power_exponent_of(u64 m) { return m ? pf_power_exponent(__longlong_as_double((long long)m)) : 0; }
 
 // one mode of the scan: counters and maxima
 template <int NR>
@@ -86,10 +110,7 @@ __device__ __forceinline__ void scan_mode(double t, unsigned int k2, unsigned in
     const int b = pf_power_shell_of_root(k2, root);
     atomicAdd(&snm[b], (u64)w);
     if (k2) atomicAdd(&sk2[b], (u64)w * k2);
-    if (fin) {   // (a plain read first: a maximum only grows, so a term that is not above what the read saw needs no atomic)
-      const u64 tb = (u64)__double_as_longlong(t);
-      if (tb > smax[b]) atomicMax(&smax[b], tb);
-    }
+    if (fin) power_max_lds(&smax[b], (u64)__double_as_longlong(t));
     else nonfin += (u64)w;
   }
   if (NR > 0 && fin && k2) {
@@ -174,7 +195,7 @@ __global__ void __launch_bounds__(PF_POWER_BLOCK) k_power_scan(PowerView v, Powe
 #pragma unroll
     for (int c = 0; c < CG; c++)
       if (pc.on[c]) {
-        const double t = power_load<F>(v, row, pc.kz[c]);
+        const double t = power_term_at<F>(v, row, pc.kz[c]);
         const unsigned int k2 = kxy2 + pc.kz2[c];
         if (bt.shells) pc.root[c] = row == r0 ? pf_power_isqrt(k2) : pf_power_isqrt_near(k2, pc.root[c]);
         scan_mode<NR>(t, k2, pc.root[c], pc.w[c], bt, smax, snm, sk2, nonfin, exy, pc.ez[c], vmx);
@@ -186,7 +207,7 @@ __global__ void __launch_bounds__(PF_POWER_BLOCK) k_power_scan(PowerView v, Powe
     const int sx = pf_power_signed((int)x, v.n), sy = pf_power_signed((int)y + v.y0, v.n);
     const unsigned int k2 = (unsigned int)(sx * sx + sy * sy) + half * half;
     power_exy<NR>(v, bt, power_abs(sx), power_abs(sy), exy);
-    scan_mode<NR>(power_load<F>(v, row, half), k2, bt.shells ? pf_power_isqrt(k2) : 0, 1, bt, smax, snm, sk2, nonfin, exy, pc.eny, vmx);
+    scan_mode<NR>(power_term_at<F>(v, row, half), k2, bt.shells ? pf_power_isqrt(k2) : 0, 1, bt, smax, snm, sk2, nonfin, exy, pc.eny, vmx);
   }
 #pragma unroll
   for (int r = 0; r < NR; r++)
@@ -221,7 +242,7 @@ __global__ void __launch_bounds__(PF_POWER_BLOCK) k_power_acc(PowerView v, Power
   u64 *sp = lds, *sv = lds + 3 * nb;
   int *se = (int *)(lds + 3 * nb + 3 * PF_POWER_NR);
   for (int k = threadIdx.x; k < 3 * nb + 3 * PF_POWER_NR; k += PF_POWER_BLOCK) lds[k] = 0;
-  for (int b = threadIdx.x; b < nb; b += PF_POWER_BLOCK) se[b] = g.smax[b] ? pf_power_exponent(__longlong_as_double((long long)g.smax[b])) : 0;
+  for (int b = threadIdx.x; b < nb; b += PF_POWER_BLOCK) se[b] = power_exponent_of(g.smax[b]);
   __syncthreads();
   unsigned int r0, r1, kx, yl;
   power_rows(v, r0, r1, kx, yl);
@@ -232,8 +253,7 @@ __global__ void __launch_bounds__(PF_POWER_BLOCK) k_power_acc(PowerView v, Power
   u64 va[NR ? NR : 1][3];
 #pragma unroll
   for (int r = 0; r < (NR ? NR : 1); r++) {
-    const u64 m = (r < bt.nr) ? g.vmax[bt.r0 + r] : 0;
-    ve[r] = m ? pf_power_exponent(__longlong_as_double((long long)m)) : 0;   // (no maximum: no positive term, nothing is added)
+    ve[r] = power_exponent_of((r < bt.nr) ? g.vmax[bt.r0 + r] : 0);
     va[r][0] = va[r][1] = va[r][2] = 0;
   }
   const unsigned int half = (unsigned int)v.n / 2;
@@ -244,7 +264,7 @@ __global__ void __launch_bounds__(PF_POWER_BLOCK) k_power_acc(PowerView v, Power
 #pragma unroll
     for (int c = 0; c < CG; c++)
       if (pc.on[c]) {
-        const double t = power_load<F>(v, row, pc.kz[c]);
+        const double t = power_term_at<F>(v, row, pc.kz[c]);
         const unsigned int k2 = kxy2 + pc.kz2[c];
         if (bt.shells) pc.root[c] = row == r0 ? pf_power_isqrt(k2) : pf_power_isqrt_near(k2, pc.root[c]);
         acc_mode<NR>(t, k2, pc.root[c], pc.w[c], bt, sp, se, exy, pc.ez[c], ve, va);
@@ -256,7 +276,7 @@ __global__ void __launch_bounds__(PF_POWER_BLOCK) k_power_acc(PowerView v, Power
     const int sx = pf_power_signed((int)x, v.n), sy = pf_power_signed((int)y + v.y0, v.n);
     const unsigned int k2 = (unsigned int)(sx * sx + sy * sy) + half * half;
     power_exy<NR>(v, bt, power_abs(sx), power_abs(sy), exy);
-    acc_mode<NR>(power_load<F>(v, row, half), k2, bt.shells ? pf_power_isqrt(k2) : 0, 1, bt, sp, se, exy, pc.eny, ve, va);
+    acc_mode<NR>(power_term_at<F>(v, row, half), k2, bt.shells ? pf_power_isqrt(k2) : 0, 1, bt, sp, se, exy, pc.eny, ve, va);
   }
 #pragma unroll
   for (int r = 0; r < NR; r++)
@@ -274,7 +294,128 @@ __global__ void __launch_bounds__(PF_POWER_BLOCK) k_power_final(int nb, int ns, 
   if (i >= nb + ns) return;
   const u64 mx = i < nb ? g.smax[i] : g.vmax[i - nb];
   const u64 *l = i < nb ? g.pl + 4 * i : g.vl + 4 * (i - nb);
-  g.out[i] = mx ? pf_power_from_limbs(l, 4, pf_power_exponent(__longlong_as_double((long long)mx))) / n6 : 0.0;
+  g.out[i] = mx ? pf_power_from_limbs(l, 4, power_exponent_of(mx)) / n6 : 0.0;
+}
+
+// ------------------------------------------------------------------------------------------------------------ two spectra ----
+// the rows of both spectra (spec: the matter's); lin null: no cross sums; C null: no deconvolution
+struct MatterView : PowerView { const void *lin; const double *C; };
+// the tables in HBM, 64-bit words: one allocation, cleared before the first scan.  smax / pl: [3][nb] and [3][4 nb] by `which`
+struct MatterTabs { u64 *smax, *nm, *k2, *pl; double *out; };
+
+__device__ __forceinline__ u64 power_wave_sum(u64 v) {
+  for (int off = warpSize / 2; off; off >>= 1) v += __shfl_down(v, off);
+  return v;
+}
+
+// the auto and the cross term of mode (row, kz); fin: both are finite (a mode with a term that is not is in no sum)
+template <class F> __device__ __forceinline__ void matter_terms(const MatterView &v, unsigned int row, unsigned int kz, double cxy, double &ta, double &tc, bool &fin) {
+  double a, b, p = 0.0, q = 0.0;
+  power_load<F>(v.spec, v.pitch, row, kz, a, b);
+  const double c = v.C ? pf_matter_deconv(cxy, 1.0, v.C[kz]) : -1.0;
+  ta = pf_matter_auto(a, b, c);
+  tc = 0.0;
+  if (v.lin) { power_load<F>(v.lin, v.pitch, row, kz, p, q); tc = pf_matter_cross(a, b, p, q, c); }
+  fin = pf_power_finite(ta) && pf_power_finite(tc);
+}
+
+// what both passes share: the rows of this workgroup one after the other, thread t at the columns kz = t, t + 256, ... <= n/2
+template <class F, class OP> __device__ __forceinline__ void matter_walk(const MatterView &v, OP op) {
+  const unsigned int r0 = blockIdx.x * v.rows_per_wg, r1 = r0 + v.rows_per_wg < v.rows ? r0 + v.rows_per_wg : v.rows;
+  const unsigned int half = (unsigned int)v.n / 2;
+  for (unsigned int row = r0; row < r1; row++) {
+    const unsigned int kx = row / (unsigned int)v.nyl, yl = row - kx * (unsigned int)v.nyl;
+    const int sx = pf_power_signed((int)kx, v.n), sy = pf_power_signed((int)yl + v.y0, v.n);
+    const unsigned int kxy2 = (unsigned int)(sx * sx + sy * sy);
+    const double cxy = v.C ? v.C[power_abs(sx)] * v.C[power_abs(sy)] : 1.0;
+    for (unsigned int kz = threadIdx.x; kz <= half; kz += PF_POWER_BLOCK) {
+      const unsigned int k2 = kxy2 + kz * kz, w = (kz > 0 && kz < half) ? 2u : 1u;
+      bool fin;
+      double ta, tc;
+      matter_terms<F>(v, row, kz, cxy, ta, tc, fin);
+      op(pf_power_shell(k2), k2, w, ta, tc, fin);
+    }
+  }
+}
+
+// ALL: the maxima of the three sums in one pass (LDS: five tables of nb words, the launch says whether they fit); else that of `which`
+// alone (three tables).  nmodes, k2sum and the modes that are not finite are counted by the pass that takes the maximum of sum 0;
+// the last into the caller's counters, the copy of this workgroup's slot (pf_internal.h)
+template <class F, bool ALL>
+__global__ void __launch_bounds__(PF_POWER_BLOCK) k_matter_scan(MatterView v, int which, int nb, MatterTabs g, u64 *counters) {
+  extern __shared__ u64 lds[];
+  constexpr int NS = ALL ? 3 : 1;
+  u64 *smax = lds, *snm = lds + NS * nb, *sk2 = lds + (NS + 1) * nb;
+  for (int k = threadIdx.x; k < (NS + 2) * nb; k += PF_POWER_BLOCK) lds[k] = 0;
+  __syncthreads();
+  const bool count = ALL || which == 0;
+  u64 nonfin = 0;
+  matter_walk<F>(v, [&](int b, unsigned int k2, unsigned int w, double ta, double tc, bool fin) {
+    if (count) {
+      atomicAdd(&snm[b], (u64)w);
+      if (k2) atomicAdd(&sk2[b], (u64)w * k2);
+      if (!fin) nonfin += (u64)w;
+    }
+    if (!fin) return;
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+      const double t = pf_matter_part(ALL ? s : which, ta, tc);
+      if (t > 0.0) power_max_lds(&smax[s * nb + b], (u64)__double_as_longlong(t));
+    }
+  });
+  nonfin = power_wave_sum(nonfin);
+  if (nonfin && (threadIdx.x & (warpSize - 1)) == 0) atomicAdd(counters + (size_t)(blockIdx.x % PF_MATTER_SLOTS) * MC_COUNT + MC_NONFIN_MODES, nonfin);
+  __syncthreads();
+  for (int b = threadIdx.x; b < nb; b += PF_POWER_BLOCK) {
+    if (count && snm[b]) { atomicAdd(&g.nm[b], snm[b]); atomicAdd(&g.k2[b], sk2[b]); }
+#pragma unroll
+    for (int s = 0; s < NS; s++)
+      if (smax[s * nb + b]) atomicMax(&g.smax[(size_t)(ALL ? s : which) * nb + b], smax[s * nb + b]);
+  }
+}
+
+template <class F>
+__global__ void __launch_bounds__(PF_POWER_BLOCK) k_matter_acc(MatterView v, int which, int nb, MatterTabs g) {
+  extern __shared__ u64 lds[];
+  u64 *sp = lds;
+  int *se = (int *)(lds + 3 * nb);
+  for (int k = threadIdx.x; k < 3 * nb; k += PF_POWER_BLOCK) lds[k] = 0;
+  for (int b = threadIdx.x; b < nb; b += PF_POWER_BLOCK) se[b] = power_exponent_of(g.smax[(size_t)which * nb + b]);
+  __syncthreads();
+  matter_walk<F>(v, [&](int b, unsigned int, unsigned int w, double ta, double tc, bool fin) {
+    const double t = pf_matter_part(which, ta, tc);
+    if (!fin || !(t > 0.0)) return;
+    uint32_t l[3];
+    pf_power_limbs((double)w * t, se[b], l);
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+      if (l[i]) atomicAdd(&sp[3 * b + i], (u64)l[i]);
+  });
+  __syncthreads();
+  for (int b = threadIdx.x; b < nb; b += PF_POWER_BLOCK) power_flush(sp + 3 * b, g.pl + 4 * ((size_t)which * nb + b));
+}
+
+// out: [nb] power, [nb] cross = positive - negative, formed once
+__global__ void __launch_bounds__(PF_POWER_BLOCK) k_matter_final(int nb, double n6, MatterTabs g) {
+  const int b = blockIdx.x * PF_POWER_BLOCK + threadIdx.x;
+  if (b >= nb) return;
+  double s[3];
+  for (int which = 0; which < 3; which++) {
+    const u64 mx = g.smax[(size_t)which * nb + b];
+    s[which] = mx ? pf_power_from_limbs(g.pl + 4 * ((size_t)which * nb + b), 4, power_exponent_of(mx)) : 0.0;
+  }
+  g.out[b] = s[0] / n6;
+  g.out[nb + b] = (s[1] - s[2]) / n6;
+}
+
+// out[i] = the largest of slots[p][i], p < P: the maximum over the ranks of `count` words, after the sum over the ranks of vectors in
+// which every rank filled its own slot alone
+__global__ void __launch_bounds__(PF_POWER_BLOCK) k_matter_slot_max(const u64 *slots, int P, int count, u64 *out) {
+  const int i = blockIdx.x * PF_POWER_BLOCK + threadIdx.x;
+  if (i >= count) return;
+  u64 m = 0;
+  for (int p = 0; p < P; p++) { const u64 v = slots[(size_t)p * count + i]; m = v > m ? v : m; }
+  out[i] = m;
 }
 
 // ------------------------------------------------------------------------------------------------------------ launches ----
@@ -319,6 +460,25 @@ static int power_check_args(const char *who, int task, int ns, const double *rad
 struct PowerScratch { u64 *words; };
 struct PowerGuard { PowerScratch *s; ~PowerGuard() { hipFree(s->words); s->words = nullptr; } };
 
+// what every shell pass begins with: the rows of a ky-slab over at most maxwg workgroups, and the two refusals -- LDS tables (`lds`
+// bytes, the largest of the passes) beyond what a workgroup may ask for, a spectrum (the one, or a of two) off the 16 bytes of a load
+static int power_view(const char *who, int task, const char *article, const void *spec, const void *lin, int n, int y0, int nyl, long long pitch, unsigned int maxwg,
+                      size_t lds, PowerView *v, unsigned int *nwg) {
+  v->spec = spec; v->n = n; v->nzh = n / 2 + 1; v->nyl = nyl; v->y0 = y0; v->pitch = pitch;
+  v->rows = (unsigned int)n * (unsigned int)nyl;
+  v->rows_per_wg = (v->rows + maxwg - 1) / maxwg;
+  *nwg = (v->rows + v->rows_per_wg - 1) / v->rows_per_wg;
+  if (lds > PF_POWER_LDS_MAX) return pf_fail(task, "%s: the %d shells of a grid of %d do not fit the LDS tables", who, pf_power_nbins(n), n);
+  if (((uintptr_t)spec | (uintptr_t)lin) & 15) return pf_fail(task, "%s: %s spectrum is not 16-byte aligned (internal error)", who, article);
+  return 0;
+}
+// a table of the host -> the device, behind the out array of a call's words (pageable memory: the copy has left the table on return)
+static int power_upload(const char *who, int task, double *dev, const std::vector<double> &tab, hipStream_t st) {
+  PWHIP(task, who, hipMemcpyAsync(dev, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
+  PWHIP(task, who, hipStreamSynchronize(st));
+  return 0;
+}
+
 struct PowerLaunch { PowerView v; int nb; unsigned int nwg; size_t lds_scan, lds_acc; PowerTabs g; hipStream_t st; };
 // the scan and the accumulation of one batch of radii: the instantiation without radii, with up to four, or with up to PF_POWER_NR
 template <class F, int CG, int NR> static int power_pair(const PowerLaunch &L, const PowerBatch &bt) {
@@ -336,16 +496,11 @@ template <class F, int CG> static int power_batch(const PowerLaunch &L, const Po
 static int power_device(const char *who, int task, int fb, const void *spec, int n, int y0, int nyl, long long pitch, int ns, const double *radius_cells,
                         PowerScratch *s, PowerTabs *g, hipStream_t st) {
   const int nb = pf_power_nbins(n);
-  PowerView v;
-  v.spec = spec; v.n = n; v.nzh = n / 2 + 1; v.nyl = nyl; v.y0 = y0; v.pitch = pitch;
-  v.rows = (unsigned int)n * (unsigned int)nyl;
-  const unsigned int maxwg = ns ? PF_POWER_MAXWG_RADII : PF_POWER_MAXWG_SHELLS;
-  v.rows_per_wg = (v.rows + maxwg - 1) / maxwg;
-  const unsigned int nwg = (v.rows + v.rows_per_wg - 1) / v.rows_per_wg;
   if (n > 8 * PF_POWER_BLOCK) return pf_fail(task, "%s: a grid of %d has more than %d columns (internal error)", who, n, 4 * PF_POWER_BLOCK);
   const size_t lds_scan = (size_t)(3 * nb + PF_POWER_NR + 1) * 8, lds_acc = (size_t)(3 * nb + 3 * PF_POWER_NR) * 8 + (size_t)nb * 4;
-  if (lds_scan > PF_POWER_LDS_MAX || lds_acc > PF_POWER_LDS_MAX) return pf_fail(task, "%s: the %d shells of a grid of %d do not fit the LDS tables", who, nb, n);
-  if ((uintptr_t)spec & 15) return pf_fail(task, "%s: the spectrum is not 16-byte aligned (internal error)", who);
+  PowerView v;
+  unsigned int nwg;
+  if (power_view(who, task, "the", spec, nullptr, n, y0, nyl, pitch, ns ? PF_POWER_MAXWG_RADII : PF_POWER_MAXWG_SHELLS, lds_scan > lds_acc ? lds_scan : lds_acc, &v, &nwg)) return 1;
   // the window tables, one per radius: E_r[j] = exp(-(a_r j^2)), a_r = (2 pi / n)^2 R_r^2
   const double kf = 2.0 * 3.14159265358979323846 / (double)n;
   std::vector<double> E((size_t)ns * v.nzh);
@@ -362,10 +517,7 @@ static int power_device(const char *who, int task, int fb, const void *spec, int
   g->smax = s->words; g->vmax = g->smax + nb; g->nm = g->vmax + ns; g->k2 = g->nm + nb; g->nonfin = g->k2 + nb; g->pl = g->nonfin + 1; g->vl = g->pl + 4 * (size_t)nb;
   g->out = (double *)(g->vl + 4 * (size_t)ns);
   double *Edev = g->out + nout;
-  if (ns) {   // (pageable memory: the copy has left E when the call returns)
-    PWHIP(task, who, hipMemcpyAsync(Edev, E.data(), E.size() * 8, hipMemcpyHostToDevice, st));
-    PWHIP(task, who, hipStreamSynchronize(st));
-  }
+  if (ns && power_upload(who, task, Edev, E, st)) return 1;
   const PowerLaunch L = {v, nb, nwg, lds_scan, lds_acc, *g, st};
   const int cg = n / 2 <= PF_POWER_BLOCK ? 1 : n / 2 <= 2 * PF_POWER_BLOCK ? 2 : 4;
   for (int r0 = 0; r0 == 0 || r0 < ns; r0 += PF_POWER_NR) {
@@ -379,6 +531,67 @@ static int power_device(const char *who, int task, int fb, const void *spec, int
   const double n3 = (double)n * (double)n * (double)n;
   hipLaunchKernelGGL(k_power_final, dim3((unsigned int)((nout + PF_POWER_BLOCK - 1) / PF_POWER_BLOCK)), dim3(PF_POWER_BLOCK), 0, st, nb, ns, n3 * n3, *g);
   if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+  return 0;
+}
+
+// ---- the sums of two spectra (pf_internal.h; pf_matter.hip calls them).  Three positive sums per shell (0 |m|^2, 1 the positive
+// cross terms, 2 the negative ones).  Words: smax [3 nb], nm [nb], k2 [nb], pl [12 nb]; then out [2 nb] doubles and the deconvolution
+// table [n/2 + 1]; with P ranks the slots of the scans' maxima behind them, [P][3 nb]
+size_t pf_matter_shells_words(int n, int P) {
+  const size_t nb = (size_t)pf_power_nbins(n);
+  return 19 * nb + (size_t)(n / 2 + 1) + (P > 1 ? (size_t)P * 3 * nb : 0);
+}
+int pf_matter_shells_device(const char *who, int task, int fb, const void *spec_m, const void *spec_lin, int n, int y0, int nyl, long long pitch, int flags, u64 *words,
+                            u64 *counters, pf_ctx *coll, PfShellSums *sums, hipStream_t st) {
+  const int nb = pf_power_nbins(n), nzh = n / 2 + 1;
+  const size_t lds = (size_t)3 * nb * 8 + (size_t)nb * 4;
+  MatterView v;
+  unsigned int nwg;
+  if (power_view(who, task, "a", spec_m, spec_lin, n, y0, nyl, pitch, PF_POWER_MAXWG_SHELLS, lds, &v, &nwg)) return 1;
+  v.lin = spec_lin; v.C = nullptr;
+  PWHIP(task, who, hipMemsetAsync(words, 0, (size_t)19 * nb * 8, st));
+  MatterTabs g;
+  g.smax = words; g.nm = g.smax + 3 * (size_t)nb; g.k2 = g.nm + nb; g.pl = g.k2 + nb; g.out = (double *)(g.pl + 12 * (size_t)nb);
+  if (flags & PF_MATTER_DECONVOLVE) {
+    std::vector<double> C(nzh);
+    for (int j = 0; j < nzh; j++) C[j] = pf_matter_deconv_entry(j, n, (flags & PF_MATTER_NGP) ? 1 : 2);
+    double *Cdev = g.out + 2 * (size_t)nb;
+    if (power_upload(who, task, Cdev, C, st)) return 1;
+    v.C = Cdev;
+  }
+  // with a second spectrum one scan takes the three maxima where its five tables fit (n up to about 1800); PF_MATTER_SCAN_EACH=1
+  // (tests only) takes the way of the larger grids: a scan per sum
+  const size_t lds_all = (size_t)5 * nb * 8;
+  const char *each = getenv("PF_MATTER_SCAN_EACH");
+  const bool fused = spec_lin && lds_all <= PF_POWER_LDS_MAX && !(each && atoi(each) != 0);
+  const dim3 gr(nwg), bl(PF_POWER_BLOCK);
+  if (fused) hipLaunchKernelGGL((fb == 8 ? k_matter_scan<double, true> : k_matter_scan<float, true>), gr, bl, lds_all, st, v, 0, nb, g, counters);
+  // more than one rank: every scan first, then the maxima of the box -- over the ranks through the slots, in which every rank fills
+  // its own alone -- so that every limb of every rank is formed under the box's exponent.  Every all-reduce runs on the context's
+  // stream, which is st
+  PfSpecView sv;
+  if (coll) pf_ctx_spec_geometry(coll, &sv);
+  for (int pass = coll ? 0 : 1; pass < 2; pass++) {
+    for (int which = 0; which < (spec_lin ? 3 : 1); which++) {
+      if (!fused && (!coll || pass == 0)) hipLaunchKernelGGL((fb == 8 ? k_matter_scan<double, false> : k_matter_scan<float, false>), gr, bl, lds, st, v, which, nb, g, counters);
+      if (pass == 1) hipLaunchKernelGGL(fb == 8 ? k_matter_acc<double> : k_matter_acc<float>, gr, bl, lds, st, v, which, nb, g);
+      if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+    }
+    if (coll && pass == 0) {
+      const size_t cnt = (size_t)3 * nb;
+      u64 *slots = words + 19 * (size_t)nb + nzh;
+      PWHIP(task, who, hipMemsetAsync(slots, 0, (size_t)sv.P * cnt * 8, st));
+      PWHIP(task, who, hipMemcpyAsync(slots + (size_t)sv.rank * cnt, g.smax, cnt * 8, hipMemcpyDeviceToDevice, st));
+      if (pf_ctx_allreduce(coll, slots, (size_t)sv.P * cnt, 1)) return 1;
+      hipLaunchKernelGGL(k_matter_slot_max, dim3((unsigned int)((cnt + PF_POWER_BLOCK - 1) / PF_POWER_BLOCK)), bl, 0, st, slots, sv.P, (int)cnt, g.smax);
+      if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+    }
+  }
+  if (coll && pf_ctx_allreduce(coll, g.nm, (size_t)14 * nb, 1)) return 1;   // nm, k2 and the limbs pl lie one behind the other
+  const double n3 = (double)n * (double)n * (double)n;
+  hipLaunchKernelGGL(k_matter_final, dim3((unsigned int)((nb + PF_POWER_BLOCK - 1) / PF_POWER_BLOCK)), bl, 0, st, nb, n3 * n3, g);
+  if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+  sums->nm = g.nm; sums->out = g.out; sums->scans = fused ? 1 : spec_lin ? 3 : 1;
   return 0;
 }
 
@@ -420,32 +633,44 @@ extern "C" int pf_power_spectrum(pf_ctx *c, int which, int ns, const double *rad
   return power_fetch(who, sv.rank, sv.n, ns, g, (u64)sv.n * sv.n * sv.n, nmodes, k2sum, power, variance, info, sv.stream);
 }
 
+// what the taps on a caller's spectra begin with (pf_internal.h): the refusals of a layout, then the production layout on the device
+// -- rows of whole 128-byte lines, and NaN patterns in the padding that no sum may see -- filled from a and, where given, b
+int pf_stage_spectra(const char *who, int field_bytes, int n, int y0, int nyl, int fields, const double *a, const double *b, size_t words, PfSpecStage *d) {
+  if (field_bytes != 4 && field_bytes != 8) return pf_fail(0, "%s: fields of %d bytes (4 or 8)", who, field_bytes);
+  if (n < 2 || n > 2048 || (n & 1)) return pf_fail(0, "%s: a grid of %d (even, 2 to 2048)", who, n);
+  if (y0 < 0 || nyl < 1 || y0 + nyl > n) return pf_fail(0, "%s: rows %d .. %d leave the grid of %d", who, y0, y0 + nyl - 1, n);
+  const int nzh = n / 2 + 1;
+  d->nzp = n / 2 + 64 / field_bytes;
+  const long long nrows = (long long)nyl * n;
+  const size_t in_bytes = (size_t)nrows * nzh * 16, field = (size_t)nrows * d->nzp * 2 * field_bytes;
+  if (hipMalloc(&d->in, in_bytes) != hipSuccess || hipMalloc(&d->spec[0], fields * field) != hipSuccess || (words && hipMalloc((void **)&d->words, words * 8) != hipSuccess)) {
+    (void)hipGetLastError();
+    return pf_fail(0, "%s: cannot allocate %zu bytes on the device", who, in_bytes + fields * field + words * 8);
+  }
+  d->spec[1] = (char *)d->spec[0] + field;
+  PWHIP(0, who, hipMemset(d->spec[0], 0xff, fields * field));
+  const double *host[2] = {a, b};
+  for (int k = 0; k < 2 && host[k]; k++) {
+    if (k) PWHIP(0, who, hipDeviceSynchronize());   // (the first import has read `in`)
+    PWHIP(0, who, hipMemcpy(d->in, host[k], in_bytes, hipMemcpyHostToDevice));
+    // [ky_local][kx][kz] of the caller -> [kx][ky_local][kz] rows of nzp
+    if (pf_launch_spec_import_t(field_bytes, (const double *)d->in, d->spec[k], n, nyl, nzh, d->nzp, nullptr)) return pf_fail(0, "%s: launch failed", who);
+  }
+  return 0;
+}
+
 extern "C" int pf_debug_power_spectrum(int field_bytes, int n, int y0, int nyl, const double *spec_host, int ns, const double *radius_cells, unsigned long long *nmodes,
                                        unsigned long long *k2sum, double *power, double *variance, pf_power_info *info) {
   const char *who = "pf_debug_power_spectrum";
   if (!spec_host) return pf_fail(0, "%s: null argument", who);
   if (power_check_args(who, 0, ns, radius_cells, nmodes, k2sum, power, variance, info)) return 1;
-  if (field_bytes != 4 && field_bytes != 8) return pf_fail(0, "%s: fields of %d bytes (4 or 8)", who, field_bytes);
-  if (n < 2 || n > 2048 || (n & 1)) return pf_fail(0, "%s: a grid of %d (even, 2 to 2048)", who, n);
-  if (y0 < 0 || nyl < 1 || y0 + nyl > n) return pf_fail(0, "%s: rows %d .. %d leave the grid of %d", who, y0, y0 + nyl - 1, n);
-  // the production layout: rows of whole 128-byte lines, and NaN patterns in the padding that no sum may see
-  const int nzh = n / 2 + 1, nzp = n / 2 + 64 / field_bytes;
-  const long long nrows = (long long)nyl * n;
-  const size_t in_bytes = (size_t)nrows * nzh * 16, field = (size_t)nrows * nzp * 2 * field_bytes;
-  struct Bufs { void *in, *spec; ~Bufs() { hipFree(in); hipFree(spec); } } d = {nullptr, nullptr};
-  if (hipMalloc(&d.in, in_bytes) != hipSuccess || hipMalloc(&d.spec, field) != hipSuccess) {
-    (void)hipGetLastError();
-    return pf_fail(0, "%s: cannot allocate %zu bytes on the device", who, in_bytes + field);
-  }
-  PWHIP(0, who, hipMemcpy(d.in, spec_host, in_bytes, hipMemcpyHostToDevice));
-  PWHIP(0, who, hipMemset(d.spec, 0xff, field));
-  // [ky_local][kx][kz] of the caller -> [kx][ky_local][kz] rows of nzp
-  if (pf_launch_spec_import_t(field_bytes, (const double *)d.in, d.spec, n, nyl, nzh, nzp, nullptr)) return pf_fail(0, "%s: launch failed", who);
+  PfSpecStage d = {};
+  if (pf_stage_spectra(who, field_bytes, n, y0, nyl, 1, spec_host, nullptr, 0, &d)) return 1;
   PowerScratch s = {nullptr};
   PowerGuard guard{&s};
   PowerTabs g;
   PowerTimer timer(power_times_on(), nullptr);
-  if (power_device(who, 0, field_bytes, d.spec, n, y0, nyl, nzp, ns, radius_cells, &s, &g, nullptr)) return 1;
+  if (power_device(who, 0, field_bytes, d.spec[0], n, y0, nyl, d.nzp, ns, radius_cells, &s, &g, nullptr)) return 1;
   timer.end();
   return power_fetch(who, 0, n, ns, g, (u64)nyl * n * n, nmodes, k2sum, power, variance, info, nullptr);
 }

@@ -210,7 +210,9 @@ def test_one_rank_is_pf_matter_power(api):
         prod = f.products().tobytes()
         before = f.device_bytes
         for kw in ({}, {"ngp": True, "cross": False}, {"deconvolve": True, "weight": (1.0, 0.5, 0.0, 0.0)}):
+            exchange = api.matter_exchange()                # (from the second turn on: what the slab call of the turn before left)
             one = f.matter_power(density=True, **kw)
+            assert api.matter_exchange() == exchange        # the one-rank entry point shares its body with the slab call and reports no exchange
             form = api.matter_form()
             got = f.matter_power_slabs(density=True, **kw)
             assert bits_equal(got, one) and np.array_equal(got["density"], one["density"]) and api.matter_form() == form
