@@ -1132,6 +1132,75 @@ int pf_debug_matter_slabs(pf_ctx *ctx, const void *vel12_slab_host, int flags, c
                           unsigned long long *grid_slab_host, pf_matter_info *info);
 int pf_debug_matter_exchange(unsigned long long out[6]);
 
+/* --- halo power spectrum and bias: pf_halo_power ---
+   The clustering of a halo catalogue, the second standard check of a run after the mass function: per mass bin the auto power of
+   the haloes, their cross power with the resident delta(k) (the bias is b(k) = cross / P_dd of pf_power_spectrum, shell by shell)
+   and the integers of the shot noise.  The reference has no code for it; the arithmetic is defined here.
+   Inputs: pos[3 count] (doubles, x y z of halo i at 3 i) and mass[count] (ints) are host arrays, as in pf_map_update -- x and n of
+     pf_catalog's records, or Pos (plus the start of the sub-box) and Mass of groups[].  Only they are uploaded, once per call: 28
+     bytes per halo.
+   Position on axis j: p = pos[3 i + j] * scale, one double product, in grid cells of the global box (scale = 1 / (InterPartDist
+     hfactor) brings the Mpc/h of a catalogue to cells; 1 when the positions are in cells already).  One wrap: if (p >= n) p -= n;
+     if (p < 0) p += n;  A halo with p
+     not finite on any axis is `nonfinite`, one with p outside [0, n] on any axis after the single wrap is `outside`; neither is
+     deposited nor enters a bin's sums.
+   Bins: bin b, 0 <= b < nbins, 1 <= nbins <= PF_HALO_MAX_BINS, takes the haloes with mass_range[2 b] <= mass <= mass_range[2 b + 1],
+     both ends inclusive.  Ranges may overlap (cumulative thresholds are the usual use).
+   Weight: W = 1, or W = mass with PF_HALO_MASS_WEIGHT.
+   Per bin: power[b nb + s] and cross[b nb + s], nb = pf_power_bins(n), and info[b].  nmodes[nb] and k2sum[nb] are returned once:
+     they depend on the grid only.
+   info[b], over the haloes whose mass lies in the range of bin b: nonfinite and outside as above; selected = the others, the
+     haloes of the bin; weight_sum = sum of W over the selected; weight2_hi 2^64 + weight2_lo = sum of W^2, a 128-bit integer
+     (formed from two 64-bit sums of the high and low 32 bits of W^2: no floating point).  The shot-noise level of power / nmodes
+     is sum W^2 / (sum W)^2; the caller forms it.
+   Assignment in integers, unit 2^30: CIC: u = p - 0.5, i0 = floor(u), d = u - i0, t = (uint32)(d 1024) truncated; factor 1024 - t
+     to the cell i0 mod n and t to (i0 + 1) mod n; the eight contributions are W times the product of three factors, 64-bit
+     integers.  PF_HALO_NGP: W << 30 into floor(p) mod n.  Every deposited halo adds exactly W 2^30: the grid is the same bits for
+     any order of the additions (and of the list).
+   Headroom is a condition: weight_sum >= 2^34 could overflow a cell, so the call returns 1 after the selection pass, the message
+     naming the bin, and nothing is deposited.  (A real catalogue has sum M <= n^3 <= 2^33.)
+   Contrast: mean = (double)(weight_sum << 30) / (double)n^3; delta = (double)cell / mean - 1.0, rounded once to the field type
+     (the file is compiled without contraction).  info[b].empty_cells and max_cell (units of 2^-30) come from that pass.
+   An empty bin (weight_sum == 0) launches no transform: zeros in power and cross, selected = 0 (modes = n^3 all the same).
+   Shells, the weights w, the deconvolution (PF_HALO_DECONVOLVE: p = 1 for NGP, 2 for CIC), the two-sided cross sums,
+     nonfinite_modes and modes: exactly pf_matter_power's -- the same passes (pf_power.hip) behind the context's own forward
+     transform.  No floating-point atomics anywhere.
+   cross == NULL needs no density; cross != NULL needs the resident delta(k).  Products are not needed.
+   Any number of ranks, collective: every rank passes the WHOLE list, in any order, and deposits only what falls on the planes of
+     its own x-slab [x0, x0 + nxl): no grid is exchanged.  The list-derived counters are equal on every rank by construction;
+     empty_cells, max_cell, nonfinite_modes and the shell tables go through the installed all-reduce as in pf_matter_power_slabs:
+     every rank returns the bits one rank returns for the same list.  Before any deposit the ranks agree in ONE all-reduce (every
+     rank fills a slot of its own: count, nbins, flags and each bin's selected and weight_sum) that these are the same everywhere
+     -- the summed value is then P times the rank's own -- ; otherwise every rank returns 1.  A rank that refuses on its own (a
+     bad argument, a failed allocation, the headroom) raises its flag in the same all-reduce and every rank returns 1.
+   The context is left as found: the grid (8 bytes per cell of the slab), the tables and the uploaded list are allocated for the
+     call and freed before it returns; delta and its spectrum live in the scratch field of the transform taps; pf_device_bytes,
+     products, resident spectra, arithmetic setting and flags are unchanged, and a sweep afterwards gives what it gave before.
+   Refused (1, pf_last_error, nothing launched): a null ctx / pos / mass / mass_range / nmodes / k2sum / power / info, unknown
+     flag bits, nbins out of range, a range with lo < 1 or hi < lo, scale not finite or <= 0, count > 2^31, cross without a
+     density, more than one rank without an exchange and all-reduce installed, a failed allocation (with the bytes).
+   pf_debug_halo_deposit: test tap without a context: the production selection and deposit for the one range [lo, hi] on the
+     planes [x0, x0 + nxl) of a grid of n (x0 + nxl <= n) -> the grid [nxl][n][n] and the counters (empty_cells and max_cell of
+     those planes; modes = nonfinite_modes = 0).
+   pf_debug_halo_times: with PF_HALO_TIMES=1 in the environment, ms[0..4] = device ms of the selection, the deposits (with the
+     clearing of the grid), the contrasts, the transforms and the shell passes of the calling thread's last pf_halo_power, summed
+     over its bins; 0 otherwise.  The upload is in none of them. */
+#define PF_HALO_NGP 1
+#define PF_HALO_DECONVOLVE 2
+#define PF_HALO_MASS_WEIGHT 4
+#define PF_HALO_MAX_BINS 8
+typedef struct {
+  unsigned long long selected, weight_sum, weight2_hi, weight2_lo, nonfinite, outside,
+                     empty_cells, max_cell, modes, nonfinite_modes;
+} pf_halo_info;
+int pf_halo_power(pf_ctx *ctx, int flags, size_t count, const double *pos, double scale, const int *mass,
+                  int nbins, const int *mass_range,
+                  unsigned long long *nmodes, unsigned long long *k2sum,
+                  double *power, double *cross, pf_halo_info *info);
+int pf_debug_halo_deposit(int n, int x0, int nxl, int flags, size_t count, const double *pos, double scale,
+                          const int *mass, int lo, int hi, unsigned long long *grid_host, pf_halo_info *info);
+int pf_debug_halo_times(double *ms);   /* PF_HALO_TIMES=1: select, deposit, contrast, transform, shells of the last call */
+
 /* --- measurement --- */
 int pf_get_cputime(pf_ctx *ctx, pf_cputime *t);
 int pf_reset_cputime(pf_ctx *ctx);

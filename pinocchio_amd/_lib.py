@@ -142,6 +142,14 @@ class MatterInfo(C.Structure):
     _fields_ = [(k, C.c_ulonglong) for k in ("deposited", "nonfinite", "outside", "empty_cells", "max_cell", "sum_hi32", "sum_lo32", "modes", "nonfinite_modes")]
 
 
+HALO_NGP, HALO_DECONVOLVE, HALO_MASS_WEIGHT, HALO_MAX_BINS = 1, 2, 4, 8   # PF_HALO_*
+
+
+class HaloInfo(C.Structure):
+    _fields_ = [(k, C.c_ulonglong) for k in ("selected", "weight_sum", "weight2_hi", "weight2_lo", "nonfinite", "outside", "empty_cells", "max_cell", "modes",
+                                              "nonfinite_modes")]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -320,6 +328,11 @@ PROTOTYPES = {
     "pf_matter_power_slabs": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _dp, _dp, _dp, C.POINTER(MatterInfo)]),
     "pf_debug_matter_slabs": (C.c_int, [_vp, _vp, C.c_int, _dp, C.POINTER(C.c_ulonglong), C.POINTER(MatterInfo)]),
     "pf_debug_matter_exchange": (C.c_int, [C.POINTER(C.c_ulonglong)]),
+    "pf_halo_power": (C.c_int, [_vp, C.c_int, C.c_size_t, _dp, C.c_double, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong),
+                                C.POINTER(C.c_ulonglong), _dp, _dp, C.POINTER(HaloInfo)]),
+    "pf_debug_halo_deposit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, _dp, C.c_double, C.POINTER(C.c_int), C.c_int, C.c_int,
+                                        C.POINTER(C.c_ulonglong), C.POINTER(HaloInfo)]),
+    "pf_debug_halo_times": (C.c_int, [_dp]),
     "pf_get_cputime": (C.c_int, [_vp, C.POINTER(CpuTime)]),
     "pf_reset_cputime": (C.c_int, [_vp]),
     "pf_kernel_stats": (C.c_int, [_vp, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),

@@ -208,6 +208,50 @@ def debug_matter_shells(spec_m, spec_lin=None, y0: int = 0, field_bytes: int = 8
     return out
 
 
+HALO_NGP, HALO_DECONVOLVE, HALO_MASS_WEIGHT, HALO_MAX_BINS = _lib.HALO_NGP, _lib.HALO_DECONVOLVE, _lib.HALO_MASS_WEIGHT, _lib.HALO_MAX_BINS
+HALO_TIME_KEYS = ("select", "deposit", "contrast", "transform", "shells")
+
+
+def halo_times():
+    """device ms of the phases of the last halo_power, summed over its bins: (select, deposit, contrast, transform, shell sums); zeros
+    without PF_HALO_TIMES=1 (pf_debug_halo_times)"""
+    ms = (C.c_double * 5)()
+    _lib.load().pf_debug_halo_times(ms)
+    return tuple(float(x) for x in ms)
+
+
+def _halo_flags(ngp, deconvolve, mass_weight):
+    return (HALO_NGP if ngp else 0) | (HALO_DECONVOLVE if deconvolve else 0) | (HALO_MASS_WEIGHT if mass_weight else 0)
+
+
+def _halo_list(pos, mass):
+    pos = np.ascontiguousarray(pos, dtype=np.float64)
+    mass = np.ascontiguousarray(mass, dtype=np.int32)
+    if pos.ndim != 2 or pos.shape[1] != 3 or mass.shape != (pos.shape[0],):
+        raise ValueError(f"positions [count][3] and masses [count], not {pos.shape} and {mass.shape}")
+    return pos, mass
+
+
+def _halo_info(info):
+    d = {k: int(getattr(info, k)) for k, _ in info._fields_}
+    d["weight2"] = (d["weight2_hi"] << 64) | d["weight2_lo"]
+    return d
+
+
+def debug_halo_deposit(n: int, pos, mass, lo: int, hi: int, scale: float = 1.0, mass_weight: bool = False, ngp: bool = False, x0: int = 0, nxl=None):
+    """the production selection and deposit of the haloes with lo <= mass <= hi on the planes [x0, x0 + nxl) of a grid of n, without a
+    context (pf_debug_halo_deposit) -> (the grid [nxl][n][n] of uint64 in units of 2^-30, the dict of pf_halo_info)"""
+    L = _lib.load()
+    pos, mass = _halo_list(pos, mass)
+    nxl = int(n) - int(x0) if nxl is None else int(nxl)
+    grid = np.zeros((max(nxl, 1), int(n), int(n)), dtype=np.uint64)
+    info = _lib.HaloInfo()
+    if L.pf_debug_halo_deposit(int(n), int(x0), nxl, _halo_flags(ngp, False, mass_weight), len(mass), _dp(pos), float(scale), mass.ctypes.data_as(C.POINTER(C.c_int)),
+                               int(lo), int(hi), grid.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(info)):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_halo_deposit failed")
+    return grid, _halo_info(info)
+
+
 _ARITH = {"fast": _lib.ARITH_FAST, "exact": _lib.ARITH_EXACT}
 # pf_census_cell: an outlier of the flavour census
 CENSUS_CELL_DTYPE = np.dtype([("cell", "<u8"), ("fast", "<f8"), ("exact", "<f8"), ("rmax_fast", "<i4"), ("rmax_exact", "<i4")], align=False)
@@ -1495,6 +1539,41 @@ class Fmax:
         self._chk(self.L.pf_debug_matter_slabs(self.h, v.ctypes.data_as(C.c_void_p), _matter_flags(ngp, False), None if w is None else _dp(w),
                                                grid.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(info)))
         return grid, _matter_info(info)
+
+    def halo_power(self, pos, mass, ranges, scale: float = 1.0, mass_weight: bool = False, cross: bool = True, ngp: bool = False, deconvolve: bool = False,
+                   box=None) -> dict:
+        """the power of a halo catalogue per mass bin and its cross power with the resident delta(k) (pf_halo_power; collective: every
+        rank passes the whole list): pos [count][3] in units that `scale` brings to grid cells, mass [count] integers, ranges
+        [nbins][2] of inclusive mass bounds -> nmodes[], k2sum[] per shell, power[b][] and cross[b][] (None without `cross`) per bin,
+        the counters of pf_halo_info as arrays over the bins (weight2 as Python integers), shot[b] = sum W^2 / (sum W)^2 -- the level
+        of power / nmodes that the discreteness alone gives, NaN for an empty bin -- and, with the box length `box`, k, pk[b],
+        pk_cross[b] and pk_shot[b] as matter_power forms them"""
+        pos, mass = _halo_list(pos, mass)
+        rg = np.ascontiguousarray(ranges, dtype=np.int32)
+        if rg.ndim != 2 or rg.shape[1] != 2:
+            raise ValueError(f"ranges [nbins][2], not {rg.shape}")
+        nbins = rg.shape[0]
+        nb = int(self.L.pf_power_bins(self.n))
+        nm, k2 = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.uint64)
+        pw, cr = np.zeros((max(nbins, 1), nb)), np.zeros((max(nbins, 1), nb))
+        info = (_lib.HaloInfo * max(nbins, 1))()
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        self._chk(self.L.pf_halo_power(self.h, _halo_flags(ngp, deconvolve, mass_weight), len(mass), _dp(pos), float(scale), ip(mass), nbins, ip(rg), up(nm), up(k2),
+                                       _dp(pw), _dp(cr) if cross else None, info))
+        per = [_halo_info(info[b]) for b in range(nbins)]
+        out = {"nmodes": nm, "k2sum": k2, "power": pw, "cross": cr if cross else None}
+        for k in per[0]:
+            out[k] = [p[k] for p in per] if k == "weight2" else np.array([p[k] for p in per], dtype=np.uint64)
+        out["shot"] = np.array([p["weight2"] / (p["weight_sum"] * p["weight_sum"]) if p["weight_sum"] else np.nan for p in per])
+        if box is not None:
+            f = nm.astype(np.float64)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                out["k"] = (2.0 * np.pi / float(box)) * np.sqrt(k2.astype(np.float64) / f)
+                out["pk"] = pw / f * float(box) ** 3
+                out["pk_cross"] = cr / f * float(box) ** 3 if cross else None
+                out["pk_shot"] = out["shot"] * float(box) ** 3
+        return out
 
     # -- measurement ------------------------------------------------------
     def cputime(self) -> dict:
