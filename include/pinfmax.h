@@ -1201,6 +1201,52 @@ int pf_debug_halo_deposit(int n, int x0, int nxl, int flags, size_t count, const
                           const int *mass, int lo, int hi, unsigned long long *grid_host, pf_halo_info *info);
 int pf_debug_halo_times(double *ms);   /* PF_HALO_TIMES=1: select, deposit, contrast, transform, shells of the last call */
 
+/* --- redshift-space multipoles of the halo power: pf_halo_multipoles ---
+   pf_halo_power with the list moved along one axis of the box by its velocities (the plane-parallel line of sight `los`, 0, 1 or
+   2) and every mode weighted by the Legendre polynomials L0, L2, L4 of mu = k_los / |k|: per mass bin the monopole, quadrupole and
+   hexadecapole sums of the auto power and of the cross power with the resident delta(k).  Everything not said here is
+   pf_halo_power's, word for word: flags, bins, weights, integer CIC / NGP, the headroom refusal, the contrast, empty bins, the
+   collective protocol, "context left as found", the refusal conventions, and pf_debug_halo_times, which reports this call too.
+   Position: vel is [3 count] like pos (the v of pf_catalog's records); only component los is read and uploaded (8 bytes per halo
+     more).  On axis j != los, or with vel == NULL, s = pos[3 i + j]; on axis los s = pos[3 i + los] + vel[3 i + los] * vfac -- the
+     product, then the sum, each rounded once.  Then p = s * scale and the single wrap of pf_halo_power.  vfac is position units per
+     velocity unit: for km/s and Mpc/h it is (1 + z) / (100 E(z)); the caller forms it.  A velocity that is not finite makes the
+     halo `nonfinite` even with vfac == 0 (NaN 0 is NaN); vel == NULL is real space.  A halo moved by more than a box is `outside`.
+   Weights: with s_los the signed wavenumber of the mode on axis los, a = s_los^2 and k2 as in pf_power_spectrum, exact integers:
+     L0 = 1; for k2 > 0  L2 = (double)(3 a - k2) / (double)(2 k2)  and  L4 = (double)(35 a^2 - 30 a k2 + 3 k2^2) / (double)(8 k2^2),
+     the integers formed in 64 bits (below 2^50 for n <= 2048), one division each; for k2 = 0  L2 = L4 = 0 and the mode enters no
+     sum of l > 0.  A mode and its Hermitian partner share mu^2, so the weights w of the half-spectrum stand.
+   Terms: t L_l, one product, of the auto and the cross term of pf_matter_power (deconvolved or not).  PF_MULTIPOLE_SUMS = 11
+     positive fixed-point sums per shell, each under the exponent of its own largest term:  0 auto l0;  1, 2 auto l2, the positive
+     and the negated negative terms;  3, 4 auto l4;  5, 6 cross l0;  7, 8 cross l2;  9, 10 cross l4.  A mode with a term that is not
+     finite is in nmodes and k2sum and in no other sum.
+   Outputs: with nb = pf_power_bins(n), power[(b 3 + l/2) nb + s] = (positive - negative) / N^6, cross likewise or NULL (then no
+     density is needed and the six cross sums are skipped).  No factor (2 l + 1): P_l = (2 l + 1) power / nmodes Box^3 is the
+     caller's.  The l = 0 rows are pf_halo_power's bits on the same positions.  nmodes and k2sum are pf_power_spectrum's.
+   The agreeing all-reduce of the ranks also covers los, the bits of vfac and whether vel is NULL.
+   Refused in addition to pf_halo_power's list (pf_last_error names pf_halo_multipoles): los outside 0..2, vfac not finite,
+     vfac != 0 with vel == NULL.
+   A shell pass carries as many of the sums as fit its LDS tables, spread evenly over the passes; the sums are integers, so the
+     grouping changes no bit.  PF_MULTIPOLE_SCAN_EACH=1 (environment, read per call, tests only): one sum per scan and per
+     accumulation.  pf_debug_multipole_form: form[0] = scans, form[1] = accumulation passes launched by the calling thread's last
+     shell pass (0: none yet).
+   pf_debug_halo_deposit_rsd: pf_debug_halo_deposit with the velocities; vel == NULL gives its grids.
+   pf_debug_multipole_shells: pf_debug_matter_shells with the weights: power and cross are [3][nb]; parts (may be NULL) is
+     [PF_MULTIPOLE_SUMS][nb], each positive sum / N^6; of info only modes and nonfinite_modes are filled. */
+#define PF_MULTIPOLE_ORDERS 3   /* l = 0, 2, 4 */
+#define PF_MULTIPOLE_SUMS  11   /* positive sums per shell, see above */
+int pf_halo_multipoles(pf_ctx *ctx, int flags, size_t count, const double *pos, const double *vel,
+                       double scale, double vfac, int los, const int *mass, int nbins, const int *mass_range,
+                       unsigned long long *nmodes, unsigned long long *k2sum,
+                       double *power, double *cross, pf_halo_info *info);
+int pf_debug_halo_deposit_rsd(int n, int x0, int nxl, int flags, size_t count, const double *pos, const double *vel,
+                              double scale, double vfac, int los, const int *mass, int lo, int hi,
+                              unsigned long long *grid_host, pf_halo_info *info);
+int pf_debug_multipole_shells(int field_bytes, int n, int y0, int nyl, const double *spec_m, const double *spec_lin,
+                              int flags, int los, unsigned long long *nmodes, unsigned long long *k2sum,
+                              double *power, double *cross, double *parts, pf_matter_info *info);
+int pf_debug_multipole_form(int *form);
+
 /* --- measurement --- */
 int pf_get_cputime(pf_ctx *ctx, pf_cputime *t);
 int pf_reset_cputime(pf_ctx *ctx);

@@ -143,6 +143,7 @@ class MatterInfo(C.Structure):
 
 
 HALO_NGP, HALO_DECONVOLVE, HALO_MASS_WEIGHT, HALO_MAX_BINS = 1, 2, 4, 8   # PF_HALO_*
+MULTIPOLE_ORDERS, MULTIPOLE_SUMS = 3, 11   # PF_MULTIPOLE_*
 
 
 class HaloInfo(C.Structure):
@@ -333,6 +334,13 @@ PROTOTYPES = {
     "pf_debug_halo_deposit": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, _dp, C.c_double, C.POINTER(C.c_int), C.c_int, C.c_int,
                                         C.POINTER(C.c_ulonglong), C.POINTER(HaloInfo)]),
     "pf_debug_halo_times": (C.c_int, [_dp]),
+    "pf_halo_multipoles": (C.c_int, [_vp, C.c_int, C.c_size_t, _dp, _dp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
+                                     C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _dp, _dp, C.POINTER(HaloInfo)]),
+    "pf_debug_halo_deposit_rsd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, _dp, _dp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
+                                            C.POINTER(C.c_ulonglong), C.POINTER(HaloInfo)]),
+    "pf_debug_multipole_shells": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _dp, _dp, _dp,
+                                            C.POINTER(MatterInfo)]),
+    "pf_debug_multipole_form": (C.c_int, [C.POINTER(C.c_int)]),
     "pf_get_cputime": (C.c_int, [_vp, C.POINTER(CpuTime)]),
     "pf_reset_cputime": (C.c_int, [_vp]),
     "pf_kernel_stats": (C.c_int, [_vp, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),

@@ -252,7 +252,68 @@ def debug_halo_deposit(n: int, pos, mass, lo: int, hi: int, scale: float = 1.0, 
     return grid, _halo_info(info)
 
 
-_ARITH = {"fast": _lib.ARITH_FAST, "exact": _lib.ARITH_EXACT}
+MULTIPOLE_ORDERS, MULTIPOLE_SUMS = _lib.MULTIPOLE_ORDERS, _lib.MULTIPOLE_SUMS
+
+
+def _halo_vel(vel, pos):
+    """velocities [count][3] beside positions of the same shape, or None: real space"""
+    if vel is None:
+        return None
+    vel = np.ascontiguousarray(vel, dtype=np.float64)
+    if vel.shape != pos.shape:
+        raise ValueError(f"velocities {vel.shape} beside positions {pos.shape}")
+    return vel
+
+
+def multipole_form():
+    """what the calling thread's last multipole shell pass launched: (scans, accumulation passes); zeros for none yet
+    (pf_debug_multipole_form)"""
+    form = (C.c_int * 2)()
+    _lib.load().pf_debug_multipole_form(form)
+    return int(form[0]), int(form[1])
+
+
+def debug_halo_deposit_rsd(n: int, pos, vel, mass, lo: int, hi: int, scale: float = 1.0, vfac: float = 0.0, los: int = 2, mass_weight: bool = False, ngp: bool = False,
+                           x0: int = 0, nxl=None):
+    """debug_halo_deposit with the list moved along axis `los` by vel * vfac (pf_debug_halo_deposit_rsd); vel None: real space"""
+    L = _lib.load()
+    pos, mass = _halo_list(pos, mass)
+    vel = _halo_vel(vel, pos)
+    nxl = int(n) - int(x0) if nxl is None else int(nxl)
+    grid = np.zeros((max(nxl, 1), int(n), int(n)), dtype=np.uint64)
+    info = _lib.HaloInfo()
+    if L.pf_debug_halo_deposit_rsd(int(n), int(x0), nxl, _halo_flags(ngp, False, mass_weight), len(mass), _dp(pos), None if vel is None else _dp(vel), float(scale), float(vfac),
+                                   int(los), mass.ctypes.data_as(C.POINTER(C.c_int)), int(lo), int(hi), grid.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(info)):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_halo_deposit_rsd failed")
+    return grid, _halo_info(info)
+
+
+def debug_multipole_shells(spec_m, spec_lin=None, y0: int = 0, field_bytes: int = 8, ngp: bool = False, deconvolve: bool = False, los: int = 2):
+    """the production multipole shell passes on the rows y0 .. y0 + nyl - 1 of two spectra, ky-slabs [nyl][n (kx)][n/2+1] complex128
+    (pf_debug_multipole_shells) -> nmodes[], k2sum[], power[3][], cross[3][] (None without spec_lin), parts[11][] (the positive
+    sums / N^6), modes and nonfinite_modes"""
+    L = _lib.load()
+    spec_m = np.ascontiguousarray(spec_m, dtype=np.complex128)
+    if spec_m.ndim != 3 or spec_m.shape[2] != spec_m.shape[1] // 2 + 1:
+        raise ValueError(f"a ky-slab [nyl][n][n/2+1], not {spec_m.shape}")
+    if spec_lin is not None:
+        spec_lin = np.ascontiguousarray(spec_lin, dtype=np.complex128)
+        if spec_lin.shape != spec_m.shape:
+            raise ValueError(f"two slabs of one shape, not {spec_m.shape} and {spec_lin.shape}")
+    nyl, n = spec_m.shape[:2]
+    nb = int(L.pf_power_bins(n))
+    nm, k2 = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.uint64)
+    pw, cr, parts = np.zeros((MULTIPOLE_ORDERS, nb)), np.zeros((MULTIPOLE_ORDERS, nb)), np.zeros((MULTIPOLE_SUMS, nb))
+    info = _lib.MatterInfo()
+    up = lambda a: a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+    two = spec_lin is not None
+    if L.pf_debug_multipole_shells(int(field_bytes), n, int(y0), nyl, _dp(spec_m.view(np.float64)), _dp(spec_lin.view(np.float64)) if two else None,
+                                   _matter_flags(ngp, deconvolve), int(los), up(nm), up(k2), _dp(pw), _dp(cr) if two else None, _dp(parts), C.byref(info)):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_multipole_shells failed")
+    return {"nmodes": nm, "k2sum": k2, "power": pw, "cross": cr if two else None, "parts": parts, "modes": int(info.modes), "nonfinite_modes": int(info.nonfinite_modes)}
+
+
+_ARITH ={"fast": _lib.ARITH_FAST, "exact": _lib.ARITH_EXACT}
 # pf_census_cell: an outlier of the flavour census
 CENSUS_CELL_DTYPE = np.dtype([("cell", "<u8"), ("fast", "<f8"), ("exact", "<f8"), ("rmax_fast", "<i4"), ("rmax_exact", "<i4")], align=False)
 _CENSUS_COUNTS = ("cells", "differing_bits", "beyond_2ulp", "rmax_differing", "nonfinite", "outliers")
@@ -1561,8 +1622,14 @@ class Fmax:
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
         self._chk(self.L.pf_halo_power(self.h, _halo_flags(ngp, deconvolve, mass_weight), len(mass), _dp(pos), float(scale), ip(mass), nbins, ip(rg), up(nm), up(k2),
                                        _dp(pw), _dp(cr) if cross else None, info))
+        return self._halo_result(nm, k2, pw, cr if cross else None, info, nbins, box)
+
+    @staticmethod
+    def _halo_result(nm, k2, pw, cr, info, nbins, box):
+        """the dict of halo_power / halo_multipoles from the filled arrays (cr None: no cross power)"""
+        cross = cr is not None
         per = [_halo_info(info[b]) for b in range(nbins)]
-        out = {"nmodes": nm, "k2sum": k2, "power": pw, "cross": cr if cross else None}
+        out = {"nmodes": nm, "k2sum": k2, "power": pw, "cross": cr}
         for k in per[0]:
             out[k] = [p[k] for p in per] if k == "weight2" else np.array([p[k] for p in per], dtype=np.uint64)
         out["shot"] = np.array([p["weight2"] / (p["weight_sum"] * p["weight_sum"]) if p["weight_sum"] else np.nan for p in per])
@@ -1574,6 +1641,29 @@ class Fmax:
                 out["pk_cross"] = cr / f * float(box) ** 3 if cross else None
                 out["pk_shot"] = out["shot"] * float(box) ** 3
         return out
+
+    def halo_multipoles(self, pos, vel, mass, ranges, scale: float = 1.0, vfac: float = 0.0, los: int = 2, mass_weight: bool = False, cross: bool = True, ngp: bool = False,
+                        deconvolve: bool = False, box=None) -> dict:
+        """the redshift-space multipoles l = 0, 2, 4 of the halo power per mass bin (pf_halo_multipoles; collective like halo_power):
+        the list is moved along axis `los` by vel * vfac (vel [count][3], or None for real space; vfac: position units per velocity
+        unit, (1 + z) / (100 E(z)) for km/s and Mpc/h) and every mode is weighted by L_l(mu).  Returns halo_power's dict with power and
+        cross shaped [nbins][3][nb] and no factor (2 l + 1): P_l = (2 l + 1) pk[b][l / 2]; with `box`, pk and pk_cross have that shape
+        too"""
+        pos, mass = _halo_list(pos, mass)
+        vel = _halo_vel(vel, pos)
+        rg = np.ascontiguousarray(ranges, dtype=np.int32)
+        if rg.ndim != 2 or rg.shape[1] != 2:
+            raise ValueError(f"ranges [nbins][2], not {rg.shape}")
+        nbins = rg.shape[0]
+        nb = int(self.L.pf_power_bins(self.n))
+        nm, k2 = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.uint64)
+        pw, cr = np.zeros((max(nbins, 1), MULTIPOLE_ORDERS, nb)), np.zeros((max(nbins, 1), MULTIPOLE_ORDERS, nb))
+        info = (_lib.HaloInfo * max(nbins, 1))()
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        self._chk(self.L.pf_halo_multipoles(self.h, _halo_flags(ngp, deconvolve, mass_weight), len(mass), _dp(pos), None if vel is None else _dp(vel), float(scale), float(vfac),
+                                            int(los), ip(mass), nbins, ip(rg), up(nm), up(k2), _dp(pw), _dp(cr) if cross else None, info))
+        return self._halo_result(nm, k2, pw, cr if cross else None, info, nbins, box)
 
     # -- measurement ------------------------------------------------------
     def cputime(self) -> dict:

@@ -3,7 +3,8 @@
 // deposited into a grid of 64-bit integers, turned into a contrast with the bin's own mean in the scratch field of the transform
 // taps, transformed by the context's forward transform and summed per shell with the resident delta(k).  The arithmetic of a halo
 // is pf_halo_core.h's; the shell sums are pf_power.hip's (pf_matter_shells_device), exactly as pf_matter.hip uses them.  The
-// reference has no counterpart.
+// reference has no counterpart.  pf_halo_multipoles is the same body (halo_spectra) with the list moved along one axis by its
+// velocities (pf_halo_pos_rsd) and the multipole shell pass (pf_multipole_shells_device) in place of the plain one.
 //
 //  k_halo_select    one halo per lane, every bin in one read of the list: the class of its position (ballots) and, per bin, the
 //                   counts and the integer sums of W and of the high and low halves of W^2, reduced over the wave by shuffles; one
@@ -45,7 +46,8 @@ enum { HS_SELECTED = 0, HS_NONFINITE, HS_OUTSIDE, HS_WSUM, HS_W2HI, HS_W2LO, HS_
 #define HS_WORDS ((size_t)PF_HALO_SLOTS * PF_HALO_MAX_BINS * HS_COUNT)
 #define MC_WORDS ((size_t)PF_MATTER_SLOTS * MC_COUNT)
 
-struct HaloList { const double *pos; const int *mass; size_t count; double scale; int n, mass_weight; };
+// vlos: the velocity component along the line of sight, one per halo (null: real space, pf_halo_power's path); los: that axis
+struct HaloList { const double *pos; const int *mass; size_t count; double scale; int n, mass_weight; const double *vlos; double vfac; int los; };
 struct HaloBins { int nbins, lo[PF_HALO_MAX_BINS], hi[PF_HALO_MAX_BINS]; };
 
 __device__ __forceinline__ void halo_add(u64 *p, u64 v) {
@@ -70,7 +72,7 @@ __device__ __forceinline__ u64 halo_wave_max(u64 v) {
 // the position and class of halo i (< count)
 __device__ __forceinline__ int halo_position(const HaloList &h, size_t i, double p[3]) {
 #pragma unroll
-  for (int j = 0; j < 3; j++) p[j] = pf_halo_pos(h.pos[3 * i + j], h.scale, h.n);
+  for (int j = 0; j < 3; j++) p[j] = pf_halo_pos_rsd(h.pos[3 * i + j], (h.vlos && j == h.los) ? h.vlos + i : nullptr, h.vfac, h.scale, h.n);
   return pf_halo_class(p, h.n);
 }
 
@@ -191,10 +193,10 @@ struct HaloTimer {
 
 // what a call holds on the device: the list, the selection counters, the grid of the slab and the words (counters and shell tables
 // of every bin, then what the ranks agree on)
-struct HaloBufs { double *pos; int *mass; u64 *sel, *grid, *words; };
+struct HaloBufs { double *pos, *vlos; int *mass; u64 *sel, *grid, *words; };
 struct HaloGuard {
   HaloBufs *b;
-  ~HaloGuard() { hipFree(b->pos); hipFree(b->mass); hipFree(b->sel); hipFree(b->grid); hipFree(b->words); memset(b, 0, sizeof(*b)); }
+  ~HaloGuard() { hipFree(b->pos); hipFree(b->vlos); hipFree(b->mass); hipFree(b->sel); hipFree(b->grid); hipFree(b->words); memset(b, 0, sizeof(*b)); }
 };
 
 static bool halo_finite(double x) { return x - x == 0.0; }
@@ -209,6 +211,18 @@ static int halo_check_list(const char *who, int task, int flags, size_t count, c
   if (!halo_finite(scale) || !(scale > 0.0)) return pf_fail(task, "%s: a scale of %g (finite and above 0)", who, scale);
   if (count > ((size_t)1 << 31)) return pf_fail(task, "%s: %zu haloes are more than 2^31", who, count);
   return 0;
+}
+// ... and of the line of sight of a redshift-space call
+static int halo_check_rsd(const char *who, int task, const double *vel, double vfac, int los) {
+  if (los < 0 || los > 2) return pf_fail(task, "%s: a line of sight along axis %d (0, 1 or 2)", who, los);
+  if (!halo_finite(vfac)) return pf_fail(task, "%s: a vfac of %g (finite)", who, vfac);
+  if (vfac != 0.0 && !vel) return pf_fail(task, "%s: a vfac of %g without velocities", who, vfac);
+  return 0;
+}
+// component los of vel[3 count] -> the device, through `pack`
+static void halo_pack_vlos(size_t count, const double *vel, int los, std::vector<double> &pack) {
+  pack.resize(count);
+  for (size_t i = 0; i < count; i++) pack[i] = vel[3 * i + los];
 }
 static unsigned int halo_blocks(size_t count) { return (unsigned int)((count + PF_HALO_BLOCK - 1) / PF_HALO_BLOCK); }   // (count <= 2^31)
 
@@ -281,9 +295,9 @@ static int halo_agree(const char *who, int task, pf_ctx *c, u64 *dev, std::vecto
   HLHIP(task, who, hipStreamSynchronize(st));
   return 0;
 }
-// what the ranks agree on before any deposit: a slot per rank -- count, nbins and flags, each bin's selected and weight_sum -- and
-// behind the slots the flag of a rank that refuses
-#define HA_SLOT (2 + 2 * PF_HALO_MAX_BINS)
+// what the ranks agree on before any deposit: a slot per rank -- count, nbins and flags, each bin's selected and weight_sum, the
+// line of sight with whether there are velocities, the bits of vfac -- and behind the slots the flag of a rank that refuses
+#define HA_SLOT (4 + 2 * PF_HALO_MAX_BINS)
 static size_t halo_agree_words(int P) { return (size_t)P * HA_SLOT + 1; }
 // a rank that refuses on its own (its message stands in pf_last_error) still meets the others in that all-reduce, with its flag
 static int halo_refuse(const char *who, pf_ctx *c, const PfSpecView &sv) {
@@ -298,9 +312,10 @@ static int halo_refuse(const char *who, pf_ctx *c, const PfSpecView &sv) {
   return 1;
 }
 
-extern "C" int pf_halo_power(pf_ctx *c, int flags, size_t count, const double *pos, double scale, const int *mass, int nbins, const int *mass_range,
-                             unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross, pf_halo_info *info) {
-  const char *who = "pf_halo_power";
+// the body of pf_halo_power (multi false: vel null, vfac 0; power and cross [nbins][nb]) and of pf_halo_multipoles (multi: the list
+// moved along axis los, the multipole shell pass, power and cross [nbins][3][nb])
+static int halo_spectra(const char *who, bool multi, pf_ctx *c, int flags, size_t count, const double *pos, const double *vel, double scale, double vfac, int los, const int *mass,
+                        int nbins, const int *mass_range, unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross, pf_halo_info *info) {
   if (!c) return pf_fail(0, "%s: null argument", who);
   PfSpecView sv;
   pf_ctx_spec_geometry(c, &sv);
@@ -316,24 +331,28 @@ extern "C" int pf_halo_power(pf_ctx *c, int flags, size_t count, const double *p
   int bad = 0;
   if (!nmodes || !k2sum || !power) bad = pf_fail(task, "%s: null argument", who);
   if (!bad) bad = halo_check_list(who, task, flags, count, pos, scale, mass, nbins, mass_range, info);
+  if (!bad && multi) bad = halo_check_rsd(who, task, vel, vfac, los);
   if (!bad && cross) bad = pf_ctx_spec_view(c, who, 0, &sv);   // "density not set" (which = 0: nothing is launched)
   HaloBufs b;
   memset(&b, 0, sizeof(b));
   HaloGuard guard{&b};
-  const size_t nb = (size_t)pf_power_nbins(n), shell_words = pf_matter_shells_words(n, P), bin_words = MC_WORDS + shell_words;
+  const size_t nb = (size_t)pf_power_nbins(n), shell_words = multi ? pf_multipole_shells_words(n, P) : pf_matter_shells_words(n, P), bin_words = MC_WORDS + shell_words;
+  const size_t orders = multi ? PF_MULTIPOLE_ORDERS : 1;
   const size_t fetch_words = (size_t)PF_HALO_MAX_BINS * (2 + (size_t)P);
   const size_t agree_words = halo_agree_words(P) > fetch_words ? halo_agree_words(P) : fetch_words;
   const size_t words = bad ? 0 : (size_t)(nbins + 1) * bin_words + agree_words;   // (the bin behind the last: the tables of a call whose bins are all empty)
-  const size_t list = count ? count : 1, bytes = list * 28 + HS_WORDS * 8 + cv.ncell * 8 + words * 8;
-  if (!bad && (hipMalloc((void **)&b.pos, list * 24) != hipSuccess || hipMalloc((void **)&b.mass, list * 4) != hipSuccess || hipMalloc((void **)&b.sel, HS_WORDS * 8) != hipSuccess ||
-               hipMalloc((void **)&b.grid, cv.ncell * 8) != hipSuccess || hipMalloc((void **)&b.words, words * 8) != hipSuccess)) {
+  const size_t list = count ? count : 1, bytes = list * (vel ? 36 : 28) + HS_WORDS * 8 + cv.ncell * 8 + words * 8;
+  if (!bad && (hipMalloc((void **)&b.pos, list * 24) != hipSuccess || (vel && hipMalloc((void **)&b.vlos, list * 8) != hipSuccess) || hipMalloc((void **)&b.mass, list * 4) != hipSuccess ||
+               hipMalloc((void **)&b.sel, HS_WORDS * 8) != hipSuccess || hipMalloc((void **)&b.grid, cv.ncell * 8) != hipSuccess || hipMalloc((void **)&b.words, words * 8) != hipSuccess)) {
     (void)hipGetLastError();
     bad = pf_fail(task, "%s: cannot allocate %zu bytes of scratch on the device", who, bytes);
   }
   if (!bad && count && (pf_ctx_h2d(c, b.pos, pos, count * 24) || pf_ctx_h2d(c, b.mass, mass, count * 4))) bad = 1;
+  // of the velocities only the component along the line of sight, packed on the way into the pinned pieces
+  if (!bad && count && vel && pf_ctx_h2d_packed(c, b.vlos, vel + los, count, 8, 24, 0, nullptr)) bad = 1;
   if (bad) return halo_refuse(who, c, sv);
   u64 *agree = b.words + (size_t)(nbins + 1) * bin_words;
-  HaloList h = {b.pos, b.mass, count, scale, n, (flags & PF_HALO_MASS_WEIGHT) != 0};
+  HaloList h = {b.pos, b.mass, count, scale, n, (flags & PF_HALO_MASS_WEIGHT) != 0, vel ? b.vlos : nullptr, vfac, los};
   HaloBins bins;
   memset(&bins, 0, sizeof(bins));
   bins.nbins = nbins;
@@ -349,6 +368,8 @@ extern "C" int pf_halo_power(pf_ctx *c, int flags, size_t count, const double *p
     else {
       mine[0] = (u64)count; mine[1] = ((u64)nbins << 8) | (u64)flags;
       for (int k = 0; k < nbins; k++) { mine[2 + k] = hi[k].selected; mine[2 + PF_HALO_MAX_BINS + k] = hi[k].weight_sum; }
+      mine[2 + 2 * PF_HALO_MAX_BINS] = ((u64)(vel != nullptr) << 8) | (u64)los;
+      memcpy(&mine[3 + 2 * PF_HALO_MAX_BINS], &vfac, 8);
     }
     const std::vector<u64> own(mine, mine + HA_SLOT);
     if (halo_agree(who, task, c, agree, a, st)) return 1;
@@ -356,7 +377,8 @@ extern "C" int pf_halo_power(pf_ctx *c, int flags, size_t count, const double *p
     if (a[a.size() - 1]) return pf_fail(task, "%s: refused on another rank of the context", who);
     for (int p = 0; p < P; p++)
       if (memcmp(a.data() + (size_t)p * HA_SLOT, own.data(), HA_SLOT * 8))
-        return pf_fail(task, "%s: rank %d holds another list, other bins or other flags than rank %d (%llu haloes there, %zu here)", who, p, sv.rank, a[(size_t)p * HA_SLOT], count);
+        return pf_fail(task, "%s: rank %d holds another list, other bins, other flags or another line of sight than rank %d (%llu haloes there, %zu here)", who, p, sv.rank,
+                       a[(size_t)p * HA_SLOT], count);
   } else if (full) return 1;
   // per bin: deposit, contrast, transform, shell sums; the tables stay on the device until every bin is through
   const u64 n3 = (u64)n * (u64)n * (u64)n;
@@ -372,8 +394,9 @@ extern "C" int pf_halo_power(pf_ctx *c, int flags, size_t count, const double *p
     timer.mark(HT_CONTRAST);
     if (pf_ctx_matter_forward(c)) return 1;
     timer.mark(HT_TRANSFORM);
-    if (pf_matter_shells_device(who, task, sv.fb, mc.field, cross ? sv.spec : nullptr, n, sv.y0, sv.nyl, sv.nzp, flags & (PF_HALO_NGP | PF_HALO_DECONVOLVE), counters + MC_WORDS,
-                                counters, coll, &g[k], st))
+    const int sflags = flags & (PF_HALO_NGP | PF_HALO_DECONVOLVE);
+    if (multi ? pf_multipole_shells_device(who, task, sv.fb, mc.field, cross ? sv.spec : nullptr, n, sv.y0, sv.nyl, sv.nzp, sflags, los, counters + MC_WORDS, counters, coll, &g[k], st)
+              : pf_matter_shells_device(who, task, sv.fb, mc.field, cross ? sv.spec : nullptr, n, sv.y0, sv.nyl, sv.nzp, sflags, counters + MC_WORDS, counters, coll, &g[k], st))
       return 1;
     timer.mark(HT_SHELLS);
     if (first < 0) first = k;
@@ -388,7 +411,8 @@ extern "C" int pf_halo_power(pf_ctx *c, int flags, size_t count, const double *p
   timer.end();
   // the fetch: the tables and the counters of every bin that ran
   std::vector<u64> hu(2 * nb), slots(MC_WORDS);
-  std::vector<double> hd(2 * nb);
+  const size_t per = orders * nb;                       // doubles of a bin in power and in cross; out holds power, then cross
+  std::vector<double> hd(2 * per);
   HLHIP(task, who, hipMemcpyAsync(hu.data(), g[first].nm, hu.size() * 8, hipMemcpyDeviceToHost, st));
   HLHIP(task, who, hipStreamSynchronize(st));
   std::vector<u64> grid_words((size_t)nbins * (2 + (size_t)P), 0);   // per bin: empty cells, modes that are not finite, the largest cell of every rank
@@ -396,14 +420,14 @@ extern "C" int pf_halo_power(pf_ctx *c, int flags, size_t count, const double *p
     hi[k].modes = n3;
     if (!hi[k].weight_sum) {
       hi[k].empty_cells = n3;
-      for (size_t s = 0; s < nb; s++) { power[(size_t)k * nb + s] = 0.0; if (cross) cross[(size_t)k * nb + s] = 0.0; }
+      for (size_t s = 0; s < per; s++) { power[(size_t)k * per + s] = 0.0; if (cross) cross[(size_t)k * per + s] = 0.0; }
       continue;
     }
     HLHIP(task, who, hipMemcpyAsync(slots.data(), b.words + (size_t)k * bin_words, MC_WORDS * 8, hipMemcpyDeviceToHost, st));
     HLHIP(task, who, hipMemcpyAsync(hd.data(), g[k].out, hd.size() * 8, hipMemcpyDeviceToHost, st));
     HLHIP(task, who, hipStreamSynchronize(st));
-    memcpy(power + (size_t)k * nb, hd.data(), nb * 8);
-    if (cross) memcpy(cross + (size_t)k * nb, hd.data() + nb, nb * 8);
+    memcpy(power + (size_t)k * per, hd.data(), per * 8);
+    if (cross) memcpy(cross + (size_t)k * per, hd.data() + per, per * 8);
     u64 *w = grid_words.data() + (size_t)k * (2 + (size_t)P);
     halo_reduce_slots(slots.data(), &w[0], &w[2 + sv.rank], &w[1]);
   }
@@ -419,30 +443,45 @@ extern "C" int pf_halo_power(pf_ctx *c, int flags, size_t count, const double *p
   return 0;
 }
 
+extern "C" int pf_halo_power(pf_ctx *c, int flags, size_t count, const double *pos, double scale, const int *mass, int nbins, const int *mass_range,
+                             unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross, pf_halo_info *info) {
+  return halo_spectra("pf_halo_power", false, c, flags, count, pos, nullptr, scale, 0.0, 0, mass, nbins, mass_range, nmodes, k2sum, power, cross, info);
+}
+extern "C" int pf_halo_multipoles(pf_ctx *c, int flags, size_t count, const double *pos, const double *vel, double scale, double vfac, int los, const int *mass, int nbins,
+                                  const int *mass_range, unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross, pf_halo_info *info) {
+  return halo_spectra("pf_halo_multipoles", true, c, flags, count, pos, vel, scale, vfac, los, mass, nbins, mass_range, nmodes, k2sum, power, cross, info);
+}
+
 // ------------------------------------------------------------------------------------------------------------ tap ----
-extern "C" int pf_debug_halo_deposit(int n, int x0, int nxl, int flags, size_t count, const double *pos, double scale, const int *mass, int lo, int hi,
-                                     unsigned long long *grid_host, pf_halo_info *info) {
-  const char *who = "pf_debug_halo_deposit";
+// the body of pf_debug_halo_deposit (rsd false) and of pf_debug_halo_deposit_rsd
+static int halo_deposit_tap(const char *who, bool rsd, int n, int x0, int nxl, int flags, size_t count, const double *pos, const double *vel, double scale, double vfac, int los,
+                            const int *mass, int lo, int hi, unsigned long long *grid_host, pf_halo_info *info) {
   if (!grid_host) return pf_fail(0, "%s: null argument", who);
   const int range[2] = {lo, hi};
   if (halo_check_list(who, 0, flags, count, pos, scale, mass, 1, range, info)) return 1;
+  if (rsd && halo_check_rsd(who, 0, vel, vfac, los)) return 1;
   if (n < 2 || n > 2048) return pf_fail(0, "%s: a grid of %d (2 to 2048)", who, n);
   if (x0 < 0 || nxl < 1 || x0 + nxl > n) return pf_fail(0, "%s: planes %d .. %d leave the grid of %d", who, x0, x0 + nxl - 1, n);
   const size_t ncell = (size_t)nxl * n * n, list = count ? count : 1;
   HaloBufs b;
   memset(&b, 0, sizeof(b));
   HaloGuard guard{&b};
-  if (hipMalloc((void **)&b.pos, list * 24) != hipSuccess || hipMalloc((void **)&b.mass, list * 4) != hipSuccess || hipMalloc((void **)&b.sel, HS_WORDS * 8) != hipSuccess ||
-      hipMalloc((void **)&b.grid, ncell * 8) != hipSuccess || hipMalloc((void **)&b.words, MC_WORDS * 8) != hipSuccess) {
+  if (hipMalloc((void **)&b.pos, list * 24) != hipSuccess || (vel && hipMalloc((void **)&b.vlos, list * 8) != hipSuccess) || hipMalloc((void **)&b.mass, list * 4) != hipSuccess ||
+      hipMalloc((void **)&b.sel, HS_WORDS * 8) != hipSuccess || hipMalloc((void **)&b.grid, ncell * 8) != hipSuccess || hipMalloc((void **)&b.words, MC_WORDS * 8) != hipSuccess) {
     (void)hipGetLastError();
-    return pf_fail(0, "%s: cannot allocate %zu bytes on the device", who, list * 28 + HS_WORDS * 8 + ncell * 8 + MC_WORDS * 8);
+    return pf_fail(0, "%s: cannot allocate %zu bytes on the device", who, list * (vel ? 36 : 28) + HS_WORDS * 8 + ncell * 8 + MC_WORDS * 8);
   }
   if (count) {
     HLHIP(0, who, hipMemcpy(b.pos, pos, count * 24, hipMemcpyHostToDevice));
     HLHIP(0, who, hipMemcpy(b.mass, mass, count * 4, hipMemcpyHostToDevice));
+    if (vel) {
+      std::vector<double> pack;
+      halo_pack_vlos(count, vel, los, pack);
+      HLHIP(0, who, hipMemcpy(b.vlos, pack.data(), count * 8, hipMemcpyHostToDevice));
+    }
   }
   HLHIP(0, who, hipMemsetAsync(b.words, 0, MC_WORDS * 8, nullptr));
-  const HaloList h = {b.pos, b.mass, count, scale, n, (flags & PF_HALO_MASS_WEIGHT) != 0};
+  const HaloList h = {b.pos, b.mass, count, scale, n, (flags & PF_HALO_MASS_WEIGHT) != 0, vel ? b.vlos : nullptr, vfac, los};
   HaloBins bins;
   memset(&bins, 0, sizeof(bins));
   bins.nbins = 1; bins.lo[0] = lo; bins.hi[0] = hi;
@@ -458,4 +497,13 @@ extern "C" int pf_debug_halo_deposit(int n, int x0, int nxl, int flags, size_t c
   halo_reduce_slots(slots.data(), &out.empty_cells, &out.max_cell, &nonfin);
   *info = out;
   return 0;
+}
+
+extern "C" int pf_debug_halo_deposit(int n, int x0, int nxl, int flags, size_t count, const double *pos, double scale, const int *mass, int lo, int hi,
+                                     unsigned long long *grid_host, pf_halo_info *info) {
+  return halo_deposit_tap("pf_debug_halo_deposit", false, n, x0, nxl, flags, count, pos, nullptr, scale, 0.0, 0, mass, lo, hi, grid_host, info);
+}
+extern "C" int pf_debug_halo_deposit_rsd(int n, int x0, int nxl, int flags, size_t count, const double *pos, const double *vel, double scale, double vfac, int los, const int *mass,
+                                         int lo, int hi, unsigned long long *grid_host, pf_halo_info *info) {
+  return halo_deposit_tap("pf_debug_halo_deposit_rsd", true, n, x0, nxl, flags, count, pos, vel, scale, vfac, los, mass, lo, hi, grid_host, info);
 }

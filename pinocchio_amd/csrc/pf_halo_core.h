@@ -5,6 +5,7 @@
 // the wrap subtracts n.
 //
 //   position   p = pos * scale (one double product); if (p >= n) p -= n; if (p < 0) p += n   (once)
+//              in redshift space (pf_halo_multipoles) pos + vel * vfac takes the place of pos on the axis of the line of sight
 //   classes    not finite on any axis: `nonfinite`; outside [0, n] on any axis after the wrap: `outside`.  Neither is deposited
 //   CIC        u = p - 0.5, i0 = floor(u), d = u - i0 (in [0, 1]: the difference may round up to 1), t = (uint32)(d 1024) truncated
 //              (the scaling is exact); factor 1024 - t to the cell i0 mod n and t to (i0 + 1) mod n.  i0 lies in [-1, n - 1] (p == n
@@ -29,6 +30,16 @@ PF_HALO_HD double pf_halo_pos(double pos, double scale, int n) {
   if (p >= box) p -= box;
   if (p < 0.0) p += box;
   return p;
+}
+
+// the same in redshift space (pf_halo_multipoles): on the axis of the line of sight the position is first moved by the velocity,
+// s = pos + v * vfac -- the product, then the sum, each rounded once -- and s takes the place of pos.  v null: the axis is not the
+// line of sight, or the list has no velocities: pf_halo_pos itself.  A velocity that is not finite makes p not finite whatever vfac
+PF_HALO_HD double pf_halo_pos_rsd(double pos, const double *v, double vfac, double scale, int n) {
+  if (!v) return pf_halo_pos(pos, scale, n);
+  const double shift = *v * vfac;
+  const double s = pos + shift;
+  return pf_halo_pos(s, scale, n);
 }
 
 // 0 deposited, 1 not finite, 2 outside [0, n]

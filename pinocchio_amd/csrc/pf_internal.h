@@ -396,6 +396,13 @@ struct PfShellSums { const unsigned long long *nm; const double *out; int scans;
 size_t pf_matter_shells_words(int n, int P);
 int pf_matter_shells_device(const char *who, int task, int fb, const void *spec_m, const void *spec_lin, int n, int y0, int nyl, long long pitch, int flags,
                             unsigned long long *words, unsigned long long *counters, pf_ctx *coll, PfShellSums *sums, hipStream_t st);
+// the same sums weighted by the Legendre polynomials of the angle to axis `los` (pf_multipole_core.h), eleven positive sums per shell
+// (five without lin), under the same collective scheme: nm as above, out ([3][nb] power, [3][nb] cross, [11][nb] the positive sums,
+// each over N^6).  words: pf_multipole_shells_words(n, ranks of coll); scans: the scan launches.  What was launched is also kept for
+// pf_debug_multipole_form
+size_t pf_multipole_shells_words(int n, int P);
+int pf_multipole_shells_device(const char *who, int task, int fb, const void *spec_m, const void *spec_lin, int n, int y0, int nyl, long long pitch, int flags, int los,
+                               unsigned long long *words, unsigned long long *counters, pf_ctx *coll, PfShellSums *sums, hipStream_t st);
 // counters of a pf_matter call on the device: PF_MATTER_SLOTS copies of each, a workgroup adds to the copy of its index -- one counter for all
 // wavefronts of a 1024^3 call is 1.7e7 atomics on one address: the contrast pass took 778 ms that way and takes 8 (profiles/matter_notes.md);
 // the copies are summed (MC_MAX: reduced) on the host.  The scans of pf_matter_shells_device add to MC_NONFIN_MODES of `counters`

@@ -34,6 +34,10 @@
 //                 counters, so every grid up to 2048 fits).  Four passes over the two spectra (profiles/matter_notes.md).
 //  k_matter_final limbs -> double, times 1 / N^6; cross = positive - negative, formed once.
 //  k_matter_slot_max  with more than one rank: the maxima of the scans over the ranks, before any limb is formed.
+// And their multipoles for pf_halo.hip (pf_multipole_shells_device; pf_multipole_core.h): on the same walk every term times the
+// Legendre weights L2, L4 of the mode's angle to one axis, eleven positive sums per shell:
+//  k_multipole_scan / k_multipole_acc  the sums [first, first + ns) of the eleven, as many as the launcher found LDS for; a signed term
+//                 goes to the one sum its sign selects.  k_multipole_final: power and cross of l = 0, 2, 4 and the eleven sums.
 //
 // Every index is in range by construction: a mode is read only in the workgroup's own rows (< rows), at a column kz <= n/2 < pitch;
 // a shell is below pf_power_nbins(n), which sized every table, since k2 <= 3 (n/2)^2; a radius index is below the batch's nr <=
@@ -49,7 +53,7 @@
 #include <vector>
 
 #include "pf_internal.h"
-#include "pf_matter_core.h"   // the two terms of a mode of two spectra; it includes pf_power_core.h
+#include "pf_multipole_core.h"   // the Legendre weights of a mode; it includes pf_matter_core.h (the two terms of a mode of two spectra) and pf_power_core.h
 
 #define PWHIP(task, who, call)                                                                                         \
   do {                                                                                                                 \
@@ -299,7 +303,7 @@ __global__ void __launch_bounds__(PF_POWER_BLOCK) k_power_final(int nb, int ns, 
 
 // ------------------------------------------------------------------------------------------------------------ two spectra ----
 // the rows of both spectra (spec: the matter's); lin null: no cross sums; C null: no deconvolution
-struct MatterView : PowerView { const void *lin; const double *C; };
+struct MatterView : PowerView { const void *lin; const double *C; int los; };   // los: the axis of the line of sight (the multipole passes)
 // the tables in HBM, 64-bit words: one allocation, cleared before the first scan.  smax / pl: [3][nb] and [3][4 nb] by `which`
 struct MatterTabs { u64 *smax, *nm, *k2, *pl; double *out; };
 
@@ -319,7 +323,8 @@ template <class F> __device__ __forceinline__ void matter_terms(const MatterView
   fin = pf_power_finite(ta) && pf_power_finite(tc);
 }
 
-// what both passes share: the rows of this workgroup one after the other, thread t at the columns kz = t, t + 256, ... <= n/2
+// what both passes share: the rows of this workgroup one after the other, thread t at the columns kz = t, t + 256, ... <= n/2; op also
+// gets a, the squared wavenumber along axis v.los (the multipole passes; the others ignore it)
 template <class F, class OP> __device__ __forceinline__ void matter_walk(const MatterView &v, OP op) {
   const unsigned int r0 = blockIdx.x * v.rows_per_wg, r1 = r0 + v.rows_per_wg < v.rows ? r0 + v.rows_per_wg : v.rows;
   const unsigned int half = (unsigned int)v.n / 2;
@@ -333,7 +338,7 @@ template <class F, class OP> __device__ __forceinline__ void matter_walk(const M
       bool fin;
       double ta, tc;
       matter_terms<F>(v, row, kz, cxy, ta, tc, fin);
-      op(pf_power_shell(k2), k2, w, ta, tc, fin);
+      op(pf_power_shell(k2), k2, pf_multipole_a(v.los, sx, sy, kz), w, ta, tc, fin);
     }
   }
 }
@@ -350,7 +355,7 @@ __global__ void __launch_bounds__(PF_POWER_BLOCK) k_matter_scan(MatterView v, in
   __syncthreads();
   const bool count = ALL || which == 0;
   u64 nonfin = 0;
-  matter_walk<F>(v, [&](int b, unsigned int k2, unsigned int w, double ta, double tc, bool fin) {
+  matter_walk<F>(v, [&](int b, unsigned int k2, unsigned int, unsigned int w, double ta, double tc, bool fin) {
     if (count) {
       atomicAdd(&snm[b], (u64)w);
       if (k2) atomicAdd(&sk2[b], (u64)w * k2);
@@ -382,7 +387,7 @@ __global__ void __launch_bounds__(PF_POWER_BLOCK) k_matter_acc(MatterView v, int
   for (int k = threadIdx.x; k < 3 * nb; k += PF_POWER_BLOCK) lds[k] = 0;
   for (int b = threadIdx.x; b < nb; b += PF_POWER_BLOCK) se[b] = power_exponent_of(g.smax[(size_t)which * nb + b]);
   __syncthreads();
-  matter_walk<F>(v, [&](int b, unsigned int, unsigned int w, double ta, double tc, bool fin) {
+  matter_walk<F>(v, [&](int b, unsigned int, unsigned int, unsigned int w, double ta, double tc, bool fin) {
     const double t = pf_matter_part(which, ta, tc);
     if (!fin || !(t > 0.0)) return;
     uint32_t l[3];
@@ -406,6 +411,94 @@ __global__ void __launch_bounds__(PF_POWER_BLOCK) k_matter_final(int nb, double 
   }
   g.out[b] = s[0] / n6;
   g.out[nb + b] = (s[1] - s[2]) / n6;
+}
+
+// ---- the multipoles of the same two spectra (pf_multipole_core.h): eleven positive sums per shell, the terms of a mode times the
+// Legendre weights of its angle to axis v.los.  The same two passes on the same walk; a launch carries the sums [first, first + ns),
+// as many as the launcher found room for in LDS.  The tables of MatterTabs are [11][nb] (smax) and [11][4 nb] (pl) here
+template <class F>
+__global__ void __launch_bounds__(PF_POWER_BLOCK) k_multipole_scan(MatterView v, int first, int ns, int nb, MatterTabs g, u64 *counters) {
+  extern __shared__ u64 lds[];
+  u64 *smax = lds, *snm = lds + (size_t)ns * nb, *sk2 = snm + nb;
+  for (int k = threadIdx.x; k < (ns + 2) * nb; k += PF_POWER_BLOCK) lds[k] = 0;
+  __syncthreads();
+  const bool count = first == 0;   // nmodes, k2sum and the modes that are not finite: by the launch that carries sum 0
+  u64 nonfin = 0;
+  matter_walk<F>(v, [&](int b, unsigned int k2, unsigned int a, unsigned int w, double ta, double tc, bool fin) {
+    if (count) {
+      atomicAdd(&snm[b], (u64)w);
+      if (k2) atomicAdd(&sk2[b], (u64)w * k2);
+      if (!fin) nonfin += (u64)w;
+    }
+    if (!fin) return;
+    double L2, L4;
+    pf_multipole_weights(a, k2, &L2, &L4);
+    double x[6];
+    pf_multipole_terms(ta, tc, L2, L4, x);
+#pragma unroll
+    for (int k = 0; k < 6; k++) {   // (a term has one sum, by its sign: at most six maxima per mode, whatever the launch carries)
+      const double t = fabs(x[k]);
+      const int s = pf_multipole_sum_of(k, x[k]) - first;
+      if (t > 0.0 && s >= 0 && s < ns) power_max_lds(&smax[s * nb + b], (u64)__double_as_longlong(t));
+    }
+  });
+  nonfin = power_wave_sum(nonfin);
+  if (nonfin && (threadIdx.x & (warpSize - 1)) == 0) atomicAdd(counters + (size_t)(blockIdx.x % PF_MATTER_SLOTS) * MC_COUNT + MC_NONFIN_MODES, nonfin);
+  __syncthreads();
+  for (int b = threadIdx.x; b < nb; b += PF_POWER_BLOCK) {
+    if (count && snm[b]) { atomicAdd(&g.nm[b], snm[b]); atomicAdd(&g.k2[b], sk2[b]); }
+    for (int s = 0; s < ns; s++)
+      if (smax[s * nb + b]) atomicMax(&g.smax[(size_t)(first + s) * nb + b], smax[s * nb + b]);
+  }
+}
+
+template <class F>
+__global__ void __launch_bounds__(PF_POWER_BLOCK) k_multipole_acc(MatterView v, int first, int ns, int nb, MatterTabs g) {
+  extern __shared__ u64 lds[];
+  u64 *sp = lds;
+  int *se = (int *)(lds + (size_t)3 * ns * nb);
+  for (int k = threadIdx.x; k < 3 * ns * nb; k += PF_POWER_BLOCK) lds[k] = 0;
+  for (int k = threadIdx.x; k < ns * nb; k += PF_POWER_BLOCK) se[k] = power_exponent_of(g.smax[(size_t)first * nb + k]);
+  __syncthreads();
+  matter_walk<F>(v, [&](int b, unsigned int k2, unsigned int a, unsigned int w, double ta, double tc, bool fin) {
+    if (!fin) return;
+    double L2, L4;
+    pf_multipole_weights(a, k2, &L2, &L4);
+    double x[6];
+    pf_multipole_terms(ta, tc, L2, L4, x);
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      const double t = fabs(x[k]);
+      const int s = pf_multipole_sum_of(k, x[k]) - first;
+      if (!(t > 0.0) || s < 0 || s >= ns) continue;
+      uint32_t l[3];
+      pf_power_limbs((double)w * t, se[s * nb + b], l);
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+        if (l[i]) atomicAdd(&sp[3 * (s * nb + b) + i], (u64)l[i]);
+    }
+  });
+  __syncthreads();
+  for (int k = threadIdx.x; k < ns * nb; k += PF_POWER_BLOCK) power_flush(sp + 3 * k, g.pl + 4 * ((size_t)first * nb + k));
+}
+
+// out: [3][nb] power and [3][nb] cross (l = 0, 2, 4: positive - negative, formed once), then [11][nb] the positive sums themselves
+__global__ void __launch_bounds__(PF_POWER_BLOCK) k_multipole_final(int nb, double n6, MatterTabs g) {
+  const int b = blockIdx.x * PF_POWER_BLOCK + threadIdx.x;
+  if (b >= nb) return;
+  double s[PF_MULTIPOLE_NSUMS];
+  double *parts = g.out + 6 * (size_t)nb;
+#pragma unroll
+  for (int which = 0; which < PF_MULTIPOLE_NSUMS; which++) {
+    const u64 mx = g.smax[(size_t)which * nb + b];
+    s[which] = mx ? pf_power_from_limbs(g.pl + 4 * ((size_t)which * nb + b), 4, power_exponent_of(mx)) : 0.0;
+    parts[(size_t)which * nb + b] = s[which] / n6;
+  }
+  g.out[b] = s[0] / n6;
+  g.out[nb + b] = (s[1] - s[2]) / n6;
+  g.out[2 * nb + b] = (s[3] - s[4]) / n6;
+#pragma unroll
+  for (int l = 0; l < 3; l++) g.out[(size_t)(3 + l) * nb + b] = (s[5 + 2 * l] - s[6 + 2 * l]) / n6;
 }
 
 // out[i] = the largest of slots[p][i], p < P: the maximum over the ranks of `count` words, after the sum over the ranks of vectors in
@@ -534,6 +627,29 @@ static int power_device(const char *who, int task, int fb, const void *spec, int
   return 0;
 }
 
+// what the two-spectrum passes share of their launches.  The deconvolution table of `flags` -> Cdev and *C (left as it is without
+// PF_MATTER_DECONVOLVE)
+static int matter_deconv_upload(const char *who, int task, int flags, int n, double *Cdev, const double **C, hipStream_t st) {
+  if (!(flags & PF_MATTER_DECONVOLVE)) return 0;
+  std::vector<double> tab(n / 2 + 1);
+  for (int j = 0; j < n / 2 + 1; j++) tab[j] = pf_matter_deconv_entry(j, n, (flags & PF_MATTER_NGP) ? 1 : 2);
+  if (power_upload(who, task, Cdev, tab, st)) return 1;
+  *C = Cdev;
+  return 0;
+}
+// smax[cnt], the maxima of this rank's scans -> those of the box: over the ranks through the slots [P][cnt], in which every rank
+// fills its own alone.  Every all-reduce runs on the context's stream, which is st
+static int matter_box_max(const char *who, int task, pf_ctx *coll, u64 *smax, size_t cnt, u64 *slots, hipStream_t st) {
+  PfSpecView sv;
+  pf_ctx_spec_geometry(coll, &sv);
+  PWHIP(task, who, hipMemsetAsync(slots, 0, (size_t)sv.P * cnt * 8, st));
+  PWHIP(task, who, hipMemcpyAsync(slots + (size_t)sv.rank * cnt, smax, cnt * 8, hipMemcpyDeviceToDevice, st));
+  if (pf_ctx_allreduce(coll, slots, (size_t)sv.P * cnt, 1)) return 1;
+  hipLaunchKernelGGL(k_matter_slot_max, dim3((unsigned int)((cnt + PF_POWER_BLOCK - 1) / PF_POWER_BLOCK)), dim3(PF_POWER_BLOCK), 0, st, slots, sv.P, (int)cnt, smax);
+  if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+  return 0;
+}
+
 // ---- the sums of two spectra (pf_internal.h; pf_matter.hip calls them).  Three positive sums per shell (0 |m|^2, 1 the positive
 // cross terms, 2 the negative ones).  Words: smax [3 nb], nm [nb], k2 [nb], pl [12 nb]; then out [2 nb] doubles and the deconvolution
 // table [n/2 + 1]; with P ranks the slots of the scans' maxima behind them, [P][3 nb]
@@ -548,17 +664,11 @@ int pf_matter_shells_device(const char *who, int task, int fb, const void *spec_
   MatterView v;
   unsigned int nwg;
   if (power_view(who, task, "a", spec_m, spec_lin, n, y0, nyl, pitch, PF_POWER_MAXWG_SHELLS, lds, &v, &nwg)) return 1;
-  v.lin = spec_lin; v.C = nullptr;
+  v.lin = spec_lin; v.C = nullptr; v.los = 0;
   PWHIP(task, who, hipMemsetAsync(words, 0, (size_t)19 * nb * 8, st));
   MatterTabs g;
   g.smax = words; g.nm = g.smax + 3 * (size_t)nb; g.k2 = g.nm + nb; g.pl = g.k2 + nb; g.out = (double *)(g.pl + 12 * (size_t)nb);
-  if (flags & PF_MATTER_DECONVOLVE) {
-    std::vector<double> C(nzh);
-    for (int j = 0; j < nzh; j++) C[j] = pf_matter_deconv_entry(j, n, (flags & PF_MATTER_NGP) ? 1 : 2);
-    double *Cdev = g.out + 2 * (size_t)nb;
-    if (power_upload(who, task, Cdev, C, st)) return 1;
-    v.C = Cdev;
-  }
+  if (matter_deconv_upload(who, task, flags, n, g.out + 2 * (size_t)nb, &v.C, st)) return 1;
   // with a second spectrum one scan takes the three maxima where its five tables fit (n up to about 1800); PF_MATTER_SCAN_EACH=1
   // (tests only) takes the way of the larger grids: a scan per sum
   const size_t lds_all = (size_t)5 * nb * 8;
@@ -566,32 +676,130 @@ int pf_matter_shells_device(const char *who, int task, int fb, const void *spec_
   const bool fused = spec_lin && lds_all <= PF_POWER_LDS_MAX && !(each && atoi(each) != 0);
   const dim3 gr(nwg), bl(PF_POWER_BLOCK);
   if (fused) hipLaunchKernelGGL((fb == 8 ? k_matter_scan<double, true> : k_matter_scan<float, true>), gr, bl, lds_all, st, v, 0, nb, g, counters);
-  // more than one rank: every scan first, then the maxima of the box -- over the ranks through the slots, in which every rank fills
-  // its own alone -- so that every limb of every rank is formed under the box's exponent.  Every all-reduce runs on the context's
-  // stream, which is st
-  PfSpecView sv;
-  if (coll) pf_ctx_spec_geometry(coll, &sv);
+  // more than one rank: every scan first, then the maxima of the box (matter_box_max), so that every limb of every rank is formed
+  // under the box's exponent
   for (int pass = coll ? 0 : 1; pass < 2; pass++) {
     for (int which = 0; which < (spec_lin ? 3 : 1); which++) {
       if (!fused && (!coll || pass == 0)) hipLaunchKernelGGL((fb == 8 ? k_matter_scan<double, false> : k_matter_scan<float, false>), gr, bl, lds, st, v, which, nb, g, counters);
       if (pass == 1) hipLaunchKernelGGL(fb == 8 ? k_matter_acc<double> : k_matter_acc<float>, gr, bl, lds, st, v, which, nb, g);
       if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
     }
-    if (coll && pass == 0) {
-      const size_t cnt = (size_t)3 * nb;
-      u64 *slots = words + 19 * (size_t)nb + nzh;
-      PWHIP(task, who, hipMemsetAsync(slots, 0, (size_t)sv.P * cnt * 8, st));
-      PWHIP(task, who, hipMemcpyAsync(slots + (size_t)sv.rank * cnt, g.smax, cnt * 8, hipMemcpyDeviceToDevice, st));
-      if (pf_ctx_allreduce(coll, slots, (size_t)sv.P * cnt, 1)) return 1;
-      hipLaunchKernelGGL(k_matter_slot_max, dim3((unsigned int)((cnt + PF_POWER_BLOCK - 1) / PF_POWER_BLOCK)), bl, 0, st, slots, sv.P, (int)cnt, g.smax);
-      if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
-    }
+    if (coll && pass == 0 && matter_box_max(who, task, coll, g.smax, (size_t)3 * nb, words + 19 * (size_t)nb + nzh, st)) return 1;
   }
   if (coll && pf_ctx_allreduce(coll, g.nm, (size_t)14 * nb, 1)) return 1;   // nm, k2 and the limbs pl lie one behind the other
   const double n3 = (double)n * (double)n * (double)n;
   hipLaunchKernelGGL(k_matter_final, dim3((unsigned int)((nb + PF_POWER_BLOCK - 1) / PF_POWER_BLOCK)), bl, 0, st, nb, n3 * n3, g);
   if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
   sums->nm = g.nm; sums->out = g.out; sums->scans = fused ? 1 : spec_lin ? 3 : 1;
+  return 0;
+}
+
+// ---- the multipoles of two spectra (pf_internal.h; pf_halo.hip calls them).  Eleven positive sums per shell (pf_multipole_core.h),
+// five without a second spectrum.  Words: smax [11 nb], nm [nb], k2 [nb], pl [44 nb]; then out [17 nb] doubles (3 nb power, 3 nb cross,
+// 11 nb the positive sums) and the deconvolution table [n/2 + 1]; with P ranks the slots of the scans' maxima behind them, [P][11 nb].
+// A launch carries as many sums as PF_MULTIPOLE_LDS_SCAN / _ACC bytes of LDS hold (a scan: a table of 8 bytes per shell and sum and two more; an
+// accumulation: 28 bytes per shell and sum), the sums spread evenly over the launches; every grid up to 2048 has room for one.  The
+// sums are integers under the exponents of the scans' maxima: how they are grouped changes no bit.  PF_MULTIPOLE_SCAN_EACH=1 (tests
+// only): one sum per launch
+#ifndef PF_MULTIPOLE_LDS_SCAN
+#define PF_MULTIPOLE_LDS_SCAN PF_POWER_LDS_MAX
+#endif
+#ifndef PF_MULTIPOLE_LDS_ACC
+#define PF_MULTIPOLE_LDS_ACC PF_POWER_LDS_MAX
+#endif
+static_assert(PF_MULTIPOLE_NSUMS == PF_MULTIPOLE_SUMS, "pf_multipole_core.h and pinfmax.h disagree");
+static thread_local int multipole_last_form[2] = {0, 0};   // scans and accumulations launched by the last call
+extern "C" int pf_debug_multipole_form(int *form) {
+  if (!form) return 1;
+  form[0] = multipole_last_form[0]; form[1] = multipole_last_form[1];
+  return 0;
+}
+// `total` sums in launches of at most `room` (at least one) each, spread evenly.  The two sums of a signed term, 2k - 1 and 2k, should
+// ride together -- a mode adds to one of them, so the second costs a launch nothing --: the launches cut the indices -1 .. total - 1
+// into runs of *per, so that an even *per splits no pair; the run [-1, 0) of *per = 1 is empty and is not launched
+static void multipole_groups(int total, size_t room, int *per) {
+  const int slots = total + 1, g = room < 1 ? 1 : room > (size_t)slots ? slots : (int)room, launches = (slots + g - 1) / g;
+  *per = (slots + launches - 1) / launches;
+}
+size_t pf_multipole_shells_words(int n, int P) {
+  const size_t nb = (size_t)pf_power_nbins(n);
+  return 74 * nb + (size_t)(n / 2 + 1) + (P > 1 ? (size_t)P * PF_MULTIPOLE_NSUMS * nb : 0);
+}
+int pf_multipole_shells_device(const char *who, int task, int fb, const void *spec_m, const void *spec_lin, int n, int y0, int nyl, long long pitch, int flags, int los, u64 *words,
+                               u64 *counters, pf_ctx *coll, PfShellSums *sums, hipStream_t st) {
+  const int nb = pf_power_nbins(n), nzh = n / 2 + 1, total = spec_lin ? PF_MULTIPOLE_NSUMS : PF_MULTIPOLE_NSUMS_AUTO;
+  const char *each = getenv("PF_MULTIPOLE_SCAN_EACH");
+  const bool one = each && atoi(each) != 0;
+  const size_t table = (size_t)nb * 8, acc1 = (size_t)nb * 28;
+  int per_scan, per_acc;
+  multipole_groups(total, one ? 1 : PF_MULTIPOLE_LDS_SCAN / table < 3 ? 1 : PF_MULTIPOLE_LDS_SCAN / table - 2, &per_scan);
+  multipole_groups(total, one ? 1 : PF_MULTIPOLE_LDS_ACC / acc1, &per_acc);
+  const size_t lds_scan = (size_t)((per_scan < total ? per_scan : total) + 2) * table, lds_acc = (size_t)(per_acc < total ? per_acc : total) * acc1;
+  MatterView v;
+  unsigned int nwg;
+  if (power_view(who, task, "a", spec_m, spec_lin, n, y0, nyl, pitch, PF_POWER_MAXWG_SHELLS, lds_scan > lds_acc ? lds_scan : lds_acc, &v, &nwg)) return 1;
+  if (los < 0 || los > 2) return pf_fail(task, "%s: a line of sight along axis %d (0, 1 or 2)", who, los);
+  v.lin = spec_lin; v.C = nullptr; v.los = los;
+  PWHIP(task, who, hipMemsetAsync(words, 0, (size_t)74 * nb * 8, st));
+  MatterTabs g;
+  g.smax = words; g.nm = g.smax + PF_MULTIPOLE_NSUMS * (size_t)nb; g.k2 = g.nm + nb; g.pl = g.k2 + nb; g.out = (double *)(g.pl + 4 * PF_MULTIPOLE_NSUMS * (size_t)nb);
+  if (matter_deconv_upload(who, task, flags, n, g.out + 17 * (size_t)nb, &v.C, st)) return 1;
+  const dim3 gr(nwg), bl(PF_POWER_BLOCK);
+  int scans = 0, accs = 0;
+  for (int v0 = -1; v0 < total; v0 += per_scan) {
+    const int first = v0 < 0 ? 0 : v0, ns = (v0 + per_scan < total ? v0 + per_scan : total) - first;
+    if (ns <= 0) continue;
+    scans++;
+    hipLaunchKernelGGL(fb == 8 ? k_multipole_scan<double> : k_multipole_scan<float>, gr, bl, lds_scan, st, v, first, ns, nb, g, counters);
+    if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+  }
+  // more than one rank: the maxima of the box before any limb is formed, as in pf_matter_shells_device
+  if (coll && matter_box_max(who, task, coll, g.smax, (size_t)PF_MULTIPOLE_NSUMS * nb, words + 74 * (size_t)nb + nzh, st)) return 1;
+  for (int v0 = -1; v0 < total; v0 += per_acc) {
+    const int first = v0 < 0 ? 0 : v0, ns = (v0 + per_acc < total ? v0 + per_acc : total) - first;
+    if (ns <= 0) continue;
+    accs++;
+    hipLaunchKernelGGL(fb == 8 ? k_multipole_acc<double> : k_multipole_acc<float>, gr, bl, lds_acc, st, v, first, ns, nb, g);
+    if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+  }
+  if (coll && pf_ctx_allreduce(coll, g.nm, (size_t)(2 + 4 * PF_MULTIPOLE_NSUMS) * nb, 1)) return 1;   // nm, k2 and the limbs pl lie one behind the other
+  const double n3 = (double)n * (double)n * (double)n;
+  hipLaunchKernelGGL(k_multipole_final, dim3((unsigned int)((nb + PF_POWER_BLOCK - 1) / PF_POWER_BLOCK)), bl, 0, st, nb, n3 * n3, g);
+  if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+  sums->nm = g.nm; sums->out = g.out; sums->scans = scans;
+  multipole_last_form[0] = scans; multipole_last_form[1] = accs;
+  return 0;
+}
+
+extern "C" int pf_debug_multipole_shells(int field_bytes, int n, int y0, int nyl, const double *spec_m, const double *spec_lin, int flags, int los, unsigned long long *nmodes,
+                                         unsigned long long *k2sum, double *power, double *cross, double *parts, pf_matter_info *info) {
+  const char *who = "pf_debug_multipole_shells";
+  if (!spec_m || !nmodes || !k2sum || !power || !info) return pf_fail(0, "%s: null argument", who);
+  if (flags & ~(PF_MATTER_NGP | PF_MATTER_DECONVOLVE)) return pf_fail(0, "%s: unknown flag bits 0x%x", who, (unsigned int)(flags & ~(PF_MATTER_NGP | PF_MATTER_DECONVOLVE)));
+  if (los < 0 || los > 2) return pf_fail(0, "%s: a line of sight along axis %d (0, 1 or 2)", who, los);
+  if (cross && !spec_lin) return pf_fail(0, "%s: cross sums without a second spectrum", who);
+  const bool two = spec_lin && cross;
+  const size_t slot_words = (size_t)PF_MATTER_SLOTS * MC_COUNT;
+  PfSpecStage d = {};
+  if (pf_stage_spectra(who, field_bytes, n, y0, nyl, 2, spec_m, two ? spec_lin : nullptr, slot_words + pf_multipole_shells_words(n, 1), &d)) return 1;
+  PWHIP(0, who, hipMemsetAsync(d.words, 0, slot_words * 8, nullptr));
+  PfShellSums g;
+  if (pf_multipole_shells_device(who, 0, field_bytes, d.spec[0], two ? d.spec[1] : nullptr, n, y0, nyl, d.nzp, flags, los, d.words + slot_words, d.words, nullptr, &g, nullptr)) return 1;
+  const size_t nb = (size_t)pf_power_nbins(n);
+  std::vector<u64> hu(2 * nb), slots(slot_words);
+  std::vector<double> hd(17 * nb);
+  PWHIP(0, who, hipMemcpyAsync(hu.data(), g.nm, hu.size() * 8, hipMemcpyDeviceToHost, nullptr));
+  PWHIP(0, who, hipMemcpyAsync(hd.data(), g.out, hd.size() * 8, hipMemcpyDeviceToHost, nullptr));
+  PWHIP(0, who, hipMemcpyAsync(slots.data(), d.words, slot_words * 8, hipMemcpyDeviceToHost, nullptr));
+  PWHIP(0, who, hipStreamSynchronize(nullptr));
+  memcpy(nmodes, hu.data(), nb * 8);
+  memcpy(k2sum, hu.data() + nb, nb * 8);
+  memcpy(power, hd.data(), 3 * nb * 8);
+  if (cross) memcpy(cross, hd.data() + 3 * nb, 3 * nb * 8);
+  if (parts) memcpy(parts, hd.data() + 6 * nb, PF_MULTIPOLE_NSUMS * nb * 8);
+  memset(info, 0, sizeof(*info));
+  info->modes = (u64)nyl * n * n;
+  for (int k = 0; k < PF_MATTER_SLOTS; k++) info->nonfinite_modes += slots[(size_t)k * MC_COUNT + MC_NONFIN_MODES];
   return 0;
 }
 
