@@ -1247,6 +1247,67 @@ int pf_debug_multipole_shells(int field_bytes, int n, int y0, int nyl, const dou
                               double *power, double *cross, double *parts, pf_matter_info *info);
 int pf_debug_multipole_form(int *form);
 
+/* --- two-point correlation function of the haloes: pf_halo_correlation ---
+   The third standard check of a catalogue: per mass bin the circular correlation of the halo contrast with itself, xi_hh, and with
+   the resident density, xi_hd, summed in shells of the separation |r| with the Legendre weights L0, L2, L4 of mu = r_los / |r| --
+   where the BAO peak and the large-scale RSD are read off.  The list, the bins, the deposit, the contrast, the forward transform and
+   the collective protocol are pf_halo_multipoles', word for word: flags, inclusive mass ranges, pos + vel * vfac on axis los (vel ==
+   NULL: real space), the single wrap and the nonfinite / outside counters, integer CIC / NGP in units of 2^30, the headroom refusal,
+   the contrast with the bin's own mean, an empty bin launching nothing and returning zeros, every rank passing the whole list, the
+   agreeing all-reduce (with los, vfac and whether vel is NULL), "context left as found", the refusal conventions.  One body serves
+   the three calls.
+   Form pass: every stored mode of delta_h(k) (the ky-slab half-spectrum) becomes ((F)(t / (double)N3), 0), N3 = n^3 as a double:
+     one division and one rounding to the field type F.  For xi: t = the auto term of pf_matter_power (with PF_HALO_DECONVOLVE the
+     deconvolution factors squared); for xi_cross: t = the cross term with the resident delta(k), the factors once.  The k = 0 mode is
+     written as zero.  A term that is not finite is written as zero and counted, with the mode's weight w, in
+     info[b].halo.nonfinite_modes (both passes add to it).  With xi_cross the cross spectrum is formed first, into one field
+     allocated for the call and freed before it returns; the auto spectrum is formed where the reverse transform works.
+   Reverse transform: the context's, with its 1 / N^3: because of the division above the real field is the circular correlation
+     sum_x delta(x) delta(x + r) / N^3 directly, and the zero-lag cell of the auto field is the variance of the contrast.
+   Shell pass, on this rank's x-slab of that field: the cell (x, y, z) lies at the signed separations s = i > n/2 ? i - n : i (n/2
+     stays positive); r2 = sx^2 + sy^2 + sz^2, its shell is that of pf_power_spectrum with r2 for k2, nb = pf_power_bins(n) shells,
+     weight 1.  L2 and L4 are pf_halo_multipoles' from a = s_los^2 and r2 (at r2 = 0, L2 = L4 = 0).  The cell's value v gives the
+     terms v, v L2, v L4, one product each; a term that is not zero enters, as its absolute value, the positive or the negative sum
+     of its order -- l = 0 can be negative here, so there are six positive sums per field, PF_CORR_SUMS = 12 for both: auto l0 +, -;
+     l2 +, -; l4 +, -; then the same six of the cross field.  A value that is not finite enters ncells and r2sum and no other sum,
+     and is counted in nonfinite_cells.  The sums are pf_power_spectrum's fixed point (exponents from a scan pass, three limbs,
+     integer adds: no floating-point atomics), as many sums per pass as the LDS tables hold; the grouping changes no bit.
+     PF_CORR_SCAN_EACH=1 (environment, read per call, tests only): one sum per scan and per accumulation.  Over the ranks the
+     per-shell maxima go through slots of the all-reduce and the integer tables are summed, as in pf_halo_multipoles: every rank
+     returns the bits of one rank.
+   Outputs: ncells[nb] and r2sum[nb], returned once (they are nmodes and k2sum of pf_power_spectrum: the whole lattice of
+     separations has the counts of the Hermitian-weighted half-spectrum).  xi[(b 3 + l/2) nb + s] = (positive - negative), formed
+     once in double; xi_cross likewise, or NULL: then no density is needed, no extra field is allocated and no second reverse
+     transform runs.  No factor (2 l + 1) and no division by ncells: xi_l(r) = (2 l + 1) xi / ncells is the caller's to form.
+     info[b].halo is what pf_halo_multipoles returns for the bin (modes = n^3); info[b].cells = n^3; info[b].nonfinite_cells is
+     summed over both fields and over the ranks.
+   Refused (1, pf_last_error names pf_halo_correlation, nothing launched): everything pf_halo_multipoles refuses; a null ncells,
+     r2sum, xi or info; xi_cross without a density.  A failed allocation names its bytes and, on several ranks, is agreed on before
+     any collective.
+   pf_debug_corr_form: test tap without a context: the production form pass on the rows y0 .. y0 + nyl - 1 of the caller's fp64
+     spectra (ky-slabs [nyl][n][n/2+1] complex, staged as pf_debug_multipole_shells stages them); which = 0 auto, 1 cross (needs
+     spec_lin); flags: PF_HALO_NGP | PF_HALO_DECONVOLVE; spec_out: the formed spectrum widened to fp64 in the same layout; of info
+     only nonfinite_modes and modes are filled.
+   pf_debug_corr_shells: test tap without a context: the production shell passes on the planes x0 .. x0 + nxl - 1 of the caller's
+     fp64 real field [nxl][n][n], converted to field_bytes on the way in -> ncells, r2sum, xi[3][nb], parts[6][nb] (the positive
+     sums; may be NULL) and the cells that are not finite.
+   pf_debug_corr_times: with PF_CORR_TIMES=1 in the environment, ms[0..5] = device ms of the selection, the deposits, the contrasts,
+     the transforms (forward and reverse), the form passes and the shell passes of the calling thread's last pf_halo_correlation,
+     summed over its bins; 0 otherwise. */
+#define PF_CORR_ORDERS 3    /* l = 0, 2, 4 */
+#define PF_CORR_SUMS   12   /* positive sums per shell: auto l0 +,-; l2 +,-; l4 +,-; then the same six for cross */
+typedef struct { pf_halo_info halo; unsigned long long cells, nonfinite_cells; } pf_corr_info;
+int pf_halo_correlation(pf_ctx *ctx, int flags, size_t count, const double *pos, const double *vel,
+                        double scale, double vfac, int los, const int *mass, int nbins, const int *mass_range,
+                        unsigned long long *ncells, unsigned long long *r2sum,
+                        double *xi, double *xi_cross, pf_corr_info *info);
+int pf_debug_corr_form(int field_bytes, int n, int y0, int nyl, const double *spec_m, const double *spec_lin,
+                       int flags, int which, double *spec_out, pf_matter_info *info);
+int pf_debug_corr_shells(int field_bytes, int n, int x0, int nxl, const double *real_host, int los,
+                         unsigned long long *ncells, unsigned long long *r2sum,
+                         double *xi, double *parts, unsigned long long *nonfinite_cells);
+int pf_debug_corr_times(double *ms);   /* PF_CORR_TIMES=1: select, deposit, contrast, transforms (forward and reverse), form, shells */
+
 /* --- measurement --- */
 int pf_get_cputime(pf_ctx *ctx, pf_cputime *t);
 int pf_reset_cputime(pf_ctx *ctx);

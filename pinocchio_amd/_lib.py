@@ -151,6 +151,13 @@ class HaloInfo(C.Structure):
                                               "nonfinite_modes")]
 
 
+CORR_ORDERS, CORR_SUMS = 3, 12   # PF_CORR_*
+
+
+class CorrInfo(C.Structure):
+    _fields_ = [("halo", HaloInfo), ("cells", C.c_ulonglong), ("nonfinite_cells", C.c_ulonglong)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -341,6 +348,12 @@ PROTOTYPES = {
     "pf_debug_multipole_shells": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _dp, _dp, _dp,
                                             C.POINTER(MatterInfo)]),
     "pf_debug_multipole_form": (C.c_int, [C.POINTER(C.c_int)]),
+    "pf_halo_correlation": (C.c_int, [_vp, C.c_int, C.c_size_t, _dp, _dp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
+                                      C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _dp, _dp, C.POINTER(CorrInfo)]),
+    "pf_debug_corr_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.POINTER(MatterInfo)]),
+    "pf_debug_corr_shells": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _dp, _dp,
+                                       C.POINTER(C.c_ulonglong)]),
+    "pf_debug_corr_times": (C.c_int, [_dp]),
     "pf_get_cputime": (C.c_int, [_vp, C.POINTER(CpuTime)]),
     "pf_reset_cputime": (C.c_int, [_vp]),
     "pf_kernel_stats": (C.c_int, [_vp, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),

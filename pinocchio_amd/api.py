@@ -313,6 +313,58 @@ def debug_multipole_shells(spec_m, spec_lin=None, y0: int = 0, field_bytes: int 
     return {"nmodes": nm, "k2sum": k2, "power": pw, "cross": cr if two else None, "parts": parts, "modes": int(info.modes), "nonfinite_modes": int(info.nonfinite_modes)}
 
 
+CORR_ORDERS, CORR_SUMS = _lib.CORR_ORDERS, _lib.CORR_SUMS
+CORR_TIME_KEYS = ("select", "deposit", "contrast", "transform", "form", "shells")
+
+
+def debug_corr_times():
+    """device ms of the phases of the last halo_correlation, summed over its bins: (select, deposit, contrast, transforms forward and
+    reverse, form passes, shell sums); zeros without PF_CORR_TIMES=1 (pf_debug_corr_times)"""
+    ms = (C.c_double * 6)()
+    _lib.load().pf_debug_corr_times(ms)
+    return tuple(float(x) for x in ms)
+
+
+def debug_corr_form(spec_m, spec_lin=None, y0: int = 0, field_bytes: int = 8, ngp: bool = False, deconvolve: bool = False, which: int = 0):
+    """the production form pass of halo_correlation on the rows y0 .. y0 + nyl - 1 of a ky-slab [nyl][n (kx)][n/2+1] complex128
+    (pf_debug_corr_form): which 0 -> |m|^2 / N^3, which 1 -> Re(m conj lin) / N^3 (needs spec_lin), deconvolved or not, rounded once to
+    the field type -> (the formed slab, complex128 with zero imaginary parts, {modes, nonfinite_modes})"""
+    L = _lib.load()
+    spec_m = np.ascontiguousarray(spec_m, dtype=np.complex128)
+    if spec_m.ndim != 3 or spec_m.shape[2] != spec_m.shape[1] // 2 + 1:
+        raise ValueError(f"a ky-slab [nyl][n][n/2+1], not {spec_m.shape}")
+    if spec_lin is not None:
+        spec_lin = np.ascontiguousarray(spec_lin, dtype=np.complex128)
+        if spec_lin.shape != spec_m.shape:
+            raise ValueError(f"two slabs of one shape, not {spec_m.shape} and {spec_lin.shape}")
+    nyl, n = spec_m.shape[:2]
+    out = np.zeros(spec_m.shape, dtype=np.complex128)
+    info = _lib.MatterInfo()
+    if L.pf_debug_corr_form(int(field_bytes), n, int(y0), nyl, _dp(spec_m.view(np.float64)), None if spec_lin is None else _dp(spec_lin.view(np.float64)),
+                            _matter_flags(ngp, deconvolve), int(which), _dp(out.view(np.float64)), C.byref(info)):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_corr_form failed")
+    return out, {"modes": int(info.modes), "nonfinite_modes": int(info.nonfinite_modes)}
+
+
+def debug_corr_shells(real, x0: int = 0, field_bytes: int = 8, los: int = 2):
+    """the production separation-space shell passes of halo_correlation on the planes x0 .. x0 + nxl - 1 of a real field [nxl][n][n]
+    float64 (pf_debug_corr_shells) -> ncells[], r2sum[], xi[3][] (positive - negative of l = 0, 2, 4), parts[6][] (the positive
+    sums) and nonfinite_cells"""
+    L = _lib.load()
+    real = np.ascontiguousarray(real, dtype=np.float64)
+    if real.ndim != 3 or real.shape[1] != real.shape[2]:
+        raise ValueError(f"planes [nxl][n][n], not {real.shape}")
+    nxl, n = real.shape[:2]
+    nb = int(L.pf_power_bins(n))
+    nc, r2 = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.uint64)
+    xi, parts = np.zeros((CORR_ORDERS, nb)), np.zeros((CORR_SUMS // 2, nb))
+    bad = C.c_ulonglong(0)
+    up = lambda a: a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+    if L.pf_debug_corr_shells(int(field_bytes), n, int(x0), nxl, _dp(real), int(los), up(nc), up(r2), _dp(xi), _dp(parts), C.byref(bad)):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_corr_shells failed")
+    return {"ncells": nc, "r2sum": r2, "xi": xi, "parts": parts, "nonfinite_cells": int(bad.value)}
+
+
 _ARITH ={"fast": _lib.ARITH_FAST, "exact": _lib.ARITH_EXACT}
 # pf_census_cell: an outlier of the flavour census
 CENSUS_CELL_DTYPE = np.dtype([("cell", "<u8"), ("fast", "<f8"), ("exact", "<f8"), ("rmax_fast", "<i4"), ("rmax_exact", "<i4")], align=False)
@@ -1664,6 +1716,45 @@ class Fmax:
         self._chk(self.L.pf_halo_multipoles(self.h, _halo_flags(ngp, deconvolve, mass_weight), len(mass), _dp(pos), None if vel is None else _dp(vel), float(scale), float(vfac),
                                             int(los), ip(mass), nbins, ip(rg), up(nm), up(k2), _dp(pw), _dp(cr) if cross else None, info))
         return self._halo_result(nm, k2, pw, cr if cross else None, info, nbins, box)
+
+    def halo_correlation(self, pos, vel, mass, ranges, scale: float = 1.0, vfac: float = 0.0, los: int = 2, mass_weight: bool = False, cross: bool = True, ngp: bool = False,
+                         deconvolve: bool = False, box=None) -> dict:
+        """the two-point correlation function of the haloes per mass bin in shells of the separation, with the Legendre weights l = 0,
+        2, 4 of the angle to axis `los` (pf_halo_correlation; collective like halo_multipoles, whose list, bins and flags these are):
+        ncells[], r2sum[] per shell, xi[b][3][] and xi_cross[b][3][] (None without `cross`: the correlation with the resident density)
+        as plain sums -- no factor (2 l + 1), no division -- and the counters of pf_corr_info as arrays over the bins (those of
+        halo_multipoles, cells, nonfinite_cells).  Formed here for convenience: xi_l[b][l/2][] = (2 l + 1) xi / ncells, xi_cross_l
+        likewise, variance[b] = xi[b][0][0] (the zero-lag cell: the variance of the contrast, shot noise included) and, with the box
+        length `box`, r[] = (box / n) sqrt(r2sum / ncells)"""
+        pos, mass = _halo_list(pos, mass)
+        vel = _halo_vel(vel, pos)
+        rg = np.ascontiguousarray(ranges, dtype=np.int32)
+        if rg.ndim != 2 or rg.shape[1] != 2:
+            raise ValueError(f"ranges [nbins][2], not {rg.shape}")
+        nbins = rg.shape[0]
+        nb = int(self.L.pf_power_bins(self.n))
+        nc, r2 = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.uint64)
+        xi, xc = np.zeros((max(nbins, 1), CORR_ORDERS, nb)), np.zeros((max(nbins, 1), CORR_ORDERS, nb))
+        info = (_lib.CorrInfo * max(nbins, 1))()
+        up = lambda a: a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        self._chk(self.L.pf_halo_correlation(self.h, _halo_flags(ngp, deconvolve, mass_weight), len(mass), _dp(pos), None if vel is None else _dp(vel), float(scale), float(vfac),
+                                             int(los), ip(mass), nbins, ip(rg), up(nc), up(r2), _dp(xi), _dp(xc) if cross else None, info))
+        per = [_halo_info(info[b].halo) for b in range(nbins)]
+        out = {"ncells": nc, "r2sum": r2, "xi": xi, "xi_cross": xc if cross else None}
+        for k in per[0]:
+            out[k] = [p[k] for p in per] if k == "weight2" else np.array([p[k] for p in per], dtype=np.uint64)
+        out["cells"] = np.array([int(info[b].cells) for b in range(nbins)], dtype=np.uint64)
+        out["nonfinite_cells"] = np.array([int(info[b].nonfinite_cells) for b in range(nbins)], dtype=np.uint64)
+        f = nc.astype(np.float64)
+        ell = (4.0 * np.arange(CORR_ORDERS) + 1.0)[None, :, None]      # 2 l + 1 for l = 0, 2, 4
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["xi_l"] = ell * xi / f
+            out["xi_cross_l"] = ell * xc / f if cross else None
+        out["variance"] = xi[:, 0, 0].copy()
+        if box is not None:
+            out["r"] = (float(box) / self.n) * np.sqrt(r2.astype(np.float64) / f)
+        return out
 
     # -- measurement ------------------------------------------------------
     def cputime(self) -> dict:

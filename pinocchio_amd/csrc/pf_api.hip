@@ -2602,6 +2602,8 @@ static void *matter_field(pf_ctx *c) { return c->P > 1 ? recv_field(c, 0, 0) : c
 void pf_ctx_matter_view(pf_ctx *c, PfMatterCtx *m) { m->field = matter_field(c); m->rpitch = rpitch(c); m->x0 = c->rank * c->nxl; m->lpt_order = c->lpt_order; }
 int pf_ctx_matter_forward(pf_ctx *c) { return forward_of(c, matter_field(c)); }
 int pf_ctx_matter_export(pf_ctx *c, double *host) { return export_real(c, matter_field(c), host); }
+void *pf_ctx_matter_reverse_field(pf_ctx *c, size_t *bytes) { if (bytes) *bytes = c->field_bytes; return c->A[0]; }
+int pf_ctx_matter_reverse(pf_ctx *c) { return reverse_of(c, c->A[0]); }
 extern "C" int pf_forward_transform(pf_ctx *c, const double *real_host, double *spec_host) {
   if (!c || !real_host || !spec_host) return 1;
   // P > 1: the y-pass writes the send blocks into A[0], so the field itself lives in receive field 0

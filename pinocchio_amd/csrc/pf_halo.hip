@@ -5,6 +5,9 @@
 // is pf_halo_core.h's; the shell sums are pf_power.hip's (pf_matter_shells_device), exactly as pf_matter.hip uses them.  The
 // reference has no counterpart.  pf_halo_multipoles is the same body (halo_spectra) with the list moved along one axis by its
 // velocities (pf_halo_pos_rsd) and the multipole shell pass (pf_multipole_shells_device) in place of the plain one.
+// pf_halo_correlation is the same body again up to the forward transform; behind it the form passes (pf_corr_form_device: delta_h(k)
+// -> |delta_h|^2 / N^3 and Re(delta_h delta*) / N^3), the context's reverse transform (pf_ctx_matter_reverse) and the shell pass in
+// separation space (pf_corr_shells_device), all three pf_power.hip's.
 //
 //  k_halo_select    one halo per lane, every bin in one read of the list: the class of its position (ballots) and, per bin, the
 //                   counts and the integer sums of W and of the high and low halves of W^2, reduced over the wave by shuffles; one
@@ -158,19 +161,28 @@ __global__ void __launch_bounds__(PF_HALO_BLOCK) k_halo_contrast(const u64 *grid
 
 // ------------------------------------------------------------------------------------------------------------ launches ----
 // PF_HALO_TIMES=1: device ms of the phases of the calling thread's last pf_halo_power, summed over its bins
+// (and of its last pf_halo_multipoles); PF_CORR_TIMES=1: of its last pf_halo_correlation, which has the form passes too and counts
+// the reverse transforms with the forward ones
 enum { HT_SELECT = 0, HT_DEPOSIT, HT_CONTRAST, HT_TRANSFORM, HT_SHELLS, HT_COUNT };
+enum { CT_FORM = HT_SHELLS, CT_SHELLS, CT_COUNT };   // the phases of the correlation call: the first four as above
 static thread_local double halo_last_ms[HT_COUNT] = {0.0, 0.0, 0.0, 0.0, 0.0};
+static thread_local double corr_last_ms[CT_COUNT] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 extern "C" int pf_debug_halo_times(double *ms) {
   if (!ms) return 1;
   for (int i = 0; i < HT_COUNT; i++) ms[i] = halo_last_ms[i];
   return 0;
 }
+extern "C" int pf_debug_corr_times(double *ms) {
+  if (!ms) return 1;
+  for (int i = 0; i < CT_COUNT; i++) ms[i] = corr_last_ms[i];
+  return 0;
+}
 struct HaloTimer {
-  std::vector<hipEvent_t> ev; std::vector<int> phase; hipStream_t st; bool on;
-  HaloTimer(hipStream_t st_) : st(st_) {
-    const char *env = getenv("PF_HALO_TIMES");
+  std::vector<hipEvent_t> ev; std::vector<int> phase; hipStream_t st; bool on; double *dst;
+  HaloTimer(hipStream_t st_, bool corr) : st(st_), dst(corr ? corr_last_ms : halo_last_ms) {
+    const char *env = getenv(corr ? "PF_CORR_TIMES" : "PF_HALO_TIMES");
     on = env && atoi(env) != 0;
-    for (int i = 0; i < HT_COUNT; i++) halo_last_ms[i] = 0.0;
+    for (int i = 0; i < (corr ? (int)CT_COUNT : (int)HT_COUNT); i++) dst[i] = 0.0;
   }
   // what ran since the last mark belongs to `ph` (-1: to none)
   void mark(int ph) {
@@ -184,7 +196,7 @@ struct HaloTimer {
     if (on && !ev.empty() && hipEventSynchronize(ev.back()) == hipSuccess)
       for (size_t k = 1; k < ev.size(); k++) {
         float ms = 0.0f;
-        if (phase[k] >= 0 && hipEventElapsedTime(&ms, ev[k - 1], ev[k]) == hipSuccess) halo_last_ms[phase[k]] += ms;
+        if (phase[k] >= 0 && hipEventElapsedTime(&ms, ev[k - 1], ev[k]) == hipSuccess) dst[phase[k]] += ms;
       }
     on = false;
   }
@@ -193,10 +205,10 @@ struct HaloTimer {
 
 // what a call holds on the device: the list, the selection counters, the grid of the slab and the words (counters and shell tables
 // of every bin, then what the ranks agree on)
-struct HaloBufs { double *pos, *vlos; int *mass; u64 *sel, *grid, *words; };
+struct HaloBufs { double *pos, *vlos; int *mass; u64 *sel, *grid, *words; void *extra; };   // extra: the cross spectrum of pf_halo_correlation
 struct HaloGuard {
   HaloBufs *b;
-  ~HaloGuard() { hipFree(b->pos); hipFree(b->vlos); hipFree(b->mass); hipFree(b->sel); hipFree(b->grid); hipFree(b->words); memset(b, 0, sizeof(*b)); }
+  ~HaloGuard() { hipFree(b->pos); hipFree(b->vlos); hipFree(b->mass); hipFree(b->sel); hipFree(b->grid); hipFree(b->words); hipFree(b->extra); memset(b, 0, sizeof(*b)); }
 };
 
 static bool halo_finite(double x) { return x - x == 0.0; }
@@ -312,11 +324,15 @@ static int halo_refuse(const char *who, pf_ctx *c, const PfSpecView &sv) {
   return 1;
 }
 
-// the body of pf_halo_power (multi false: vel null, vfac 0; power and cross [nbins][nb]) and of pf_halo_multipoles (multi: the list
-// moved along axis los, the multipole shell pass, power and cross [nbins][3][nb])
-static int halo_spectra(const char *who, bool multi, pf_ctx *c, int flags, size_t count, const double *pos, const double *vel, double scale, double vfac, int los, const int *mass,
-                        int nbins, const int *mass_range, unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross, pf_halo_info *info) {
+// the body of pf_halo_power (HM_POWER: vel null, vfac 0; power and cross [nbins][nb]), of pf_halo_multipoles (HM_MULTI: the list
+// moved along axis los, the multipole shell pass, power and cross [nbins][3][nb]) and of pf_halo_correlation (HM_CORR: the list moved
+// likewise; behind the forward transform the form passes, the reverse transforms and the shell pass in separation space; nmodes and
+// k2sum are ncells and r2sum, power and cross xi and xi_cross [nbins][3][nb]; nonfinite_cells [nbins], null otherwise)
+enum { HM_POWER = 0, HM_MULTI, HM_CORR };
+static int halo_spectra(const char *who, int mode, pf_ctx *c, int flags, size_t count, const double *pos, const double *vel, double scale, double vfac, int los, const int *mass,
+                        int nbins, const int *mass_range, unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross, pf_halo_info *info, u64 *nonfinite_cells = nullptr) {
   if (!c) return pf_fail(0, "%s: null argument", who);
+  const bool multi = mode != HM_POWER, corr = mode == HM_CORR;
   PfSpecView sv;
   pf_ctx_spec_geometry(c, &sv);
   if (sv.P > 1 && !pf_ctx_exchange_installed(c))
@@ -336,14 +352,21 @@ static int halo_spectra(const char *who, bool multi, pf_ctx *c, int flags, size_
   HaloBufs b;
   memset(&b, 0, sizeof(b));
   HaloGuard guard{&b};
-  const size_t nb = (size_t)pf_power_nbins(n), shell_words = multi ? pf_multipole_shells_words(n, P) : pf_matter_shells_words(n, P), bin_words = MC_WORDS + shell_words;
+  // (the correlation call: the tables of the auto field, then those of the cross field, each of corr_words)
+  const size_t nb = (size_t)pf_power_nbins(n), corr_words = pf_corr_shells_words(n, P);
+  const size_t shell_words = corr ? 2 * corr_words : multi ? pf_multipole_shells_words(n, P) : pf_matter_shells_words(n, P), bin_words = MC_WORDS + shell_words;
   const size_t orders = multi ? PF_MULTIPOLE_ORDERS : 1;
   const size_t fetch_words = (size_t)PF_HALO_MAX_BINS * (2 + (size_t)P);
   const size_t agree_words = halo_agree_words(P) > fetch_words ? halo_agree_words(P) : fetch_words;
-  const size_t words = bad ? 0 : (size_t)(nbins + 1) * bin_words + agree_words;   // (the bin behind the last: the tables of a call whose bins are all empty)
-  const size_t list = count ? count : 1, bytes = list * (vel ? 36 : 28) + HS_WORDS * 8 + cv.ncell * 8 + words * 8;
+  const size_t deconv_words = corr ? (size_t)(n / 2 + 1) : 0;                      // the deconvolution table of the form passes, behind everything
+  const size_t words = bad ? 0 : (size_t)(nbins + 1) * bin_words + agree_words + deconv_words;   // (the bin behind the last: the tables of a call whose bins are all empty)
+  size_t field_bytes = 0;
+  void *rev = corr ? pf_ctx_matter_reverse_field(c, &field_bytes) : nullptr;       // where the reverse transform works
+  const size_t extra_bytes = corr && cross ? field_bytes : 0;
+  const size_t list = count ? count : 1, bytes = list * (vel ? 36 : 28) + HS_WORDS * 8 + cv.ncell * 8 + words * 8 + extra_bytes;
   if (!bad && (hipMalloc((void **)&b.pos, list * 24) != hipSuccess || (vel && hipMalloc((void **)&b.vlos, list * 8) != hipSuccess) || hipMalloc((void **)&b.mass, list * 4) != hipSuccess ||
-               hipMalloc((void **)&b.sel, HS_WORDS * 8) != hipSuccess || hipMalloc((void **)&b.grid, cv.ncell * 8) != hipSuccess || hipMalloc((void **)&b.words, words * 8) != hipSuccess)) {
+               hipMalloc((void **)&b.sel, HS_WORDS * 8) != hipSuccess || hipMalloc((void **)&b.grid, cv.ncell * 8) != hipSuccess || hipMalloc((void **)&b.words, words * 8) != hipSuccess ||
+               (extra_bytes && hipMalloc(&b.extra, extra_bytes) != hipSuccess))) {
     (void)hipGetLastError();
     bad = pf_fail(task, "%s: cannot allocate %zu bytes of scratch on the device", who, bytes);
   }
@@ -358,7 +381,7 @@ static int halo_spectra(const char *who, bool multi, pf_ctx *c, int flags, size_
   bins.nbins = nbins;
   for (int k = 0; k < nbins; k++) { bins.lo[k] = mass_range[2 * k]; bins.hi[k] = mass_range[2 * k + 1]; }
   HLHIP(task, who, hipMemsetAsync(b.words, 0, (size_t)(nbins + 1) * bin_words * 8, st));
-  HaloTimer timer(st);
+  HaloTimer timer(st, corr);
   std::vector<pf_halo_info> hi(nbins);
   const int full = halo_select(who, task, h, bins, b.sel, hi.data(), &timer, st);
   if (P > 1) {   // the same list on every rank, and no rank that refuses
@@ -383,7 +406,13 @@ static int halo_spectra(const char *who, bool multi, pf_ctx *c, int flags, size_
   // per bin: deposit, contrast, transform, shell sums; the tables stay on the device until every bin is through
   const u64 n3 = (u64)n * (u64)n * (u64)n;
   pf_ctx *coll = P > 1 ? c : nullptr;
-  std::vector<PfShellSums> g(nbins + 1);
+  std::vector<PfShellSums> g(nbins + 1), gx(nbins + 1);   // gx: the cross field of the correlation call
+  const double *Ctab = nullptr;
+  if (corr) {
+    if (pf_corr_deconv_upload(who, task, flags & (PF_HALO_NGP | PF_HALO_DECONVOLVE), n, (double *)(agree + agree_words), &Ctab, st)) return 1;
+    if (b.extra) HLHIP(task, who, hipMemsetAsync(b.extra, 0, extra_bytes, st));   // (the padding of its rows: the form pass writes the modes alone)
+    timer.mark(-1);
+  }
   int first = -1;
   for (int k = 0; k < nbins; k++) {
     if (!hi[k].weight_sum) continue;
@@ -395,6 +424,28 @@ static int halo_spectra(const char *who, bool multi, pf_ctx *c, int flags, size_
     if (pf_ctx_matter_forward(c)) return 1;
     timer.mark(HT_TRANSFORM);
     const int sflags = flags & (PF_HALO_NGP | PF_HALO_DECONVOLVE);
+    if (corr) {
+      // the cross spectrum first, into the field of its own; then the auto spectrum where the reverse transform works (with one
+      // rank that is where delta_h(k) stands: in place).  The reverse transform overwrites mc.field with more than one rank: by
+      // then both are formed
+      u64 *tabs = counters + MC_WORDS;
+      if (cross && pf_corr_form_device(who, task, sv.fb, mc.field, sv.spec, b.extra, n, sv.y0, sv.nyl, sv.nzp, Ctab, 1, counters, st)) return 1;
+      if (pf_corr_form_device(who, task, sv.fb, mc.field, nullptr, rev, n, sv.y0, sv.nyl, sv.nzp, Ctab, 0, counters, st)) return 1;
+      timer.mark(CT_FORM);
+      if (pf_ctx_matter_reverse(c)) return 1;
+      timer.mark(HT_TRANSFORM);
+      if (pf_corr_shells_device(who, task, sv.fb, rev, n, mc.x0, cv.nxl, mc.rpitch, los, tabs, coll, &g[k], st)) return 1;
+      timer.mark(CT_SHELLS);
+      if (cross) {
+        HLHIP(task, who, hipMemcpyAsync(rev, b.extra, field_bytes, hipMemcpyDeviceToDevice, st));
+        if (pf_ctx_matter_reverse(c)) return 1;
+        timer.mark(HT_TRANSFORM);
+        if (pf_corr_shells_device(who, task, sv.fb, rev, n, mc.x0, cv.nxl, mc.rpitch, los, tabs + corr_words, coll, &gx[k], st)) return 1;
+        timer.mark(CT_SHELLS);
+      }
+      if (first < 0) first = k;
+      continue;
+    }
     if (multi ? pf_multipole_shells_device(who, task, sv.fb, mc.field, cross ? sv.spec : nullptr, n, sv.y0, sv.nyl, sv.nzp, sflags, los, counters + MC_WORDS, counters, coll, &g[k], st)
               : pf_matter_shells_device(who, task, sv.fb, mc.field, cross ? sv.spec : nullptr, n, sv.y0, sv.nyl, sv.nzp, sflags, counters + MC_WORDS, counters, coll, &g[k], st))
       return 1;
@@ -404,8 +455,13 @@ static int halo_spectra(const char *who, bool multi, pf_ctx *c, int flags, size_
   if (first < 0) {   // every bin is empty: nmodes and k2sum, which depend on the grid alone, from the shell pass over a spectrum of zeros
     first = nbins;
     u64 *counters = b.words + (size_t)nbins * bin_words;
-    HLHIP(task, who, hipMemsetAsync(mc.field, 0, (size_t)n * sv.nyl * sv.nzp * 2 * sv.fb, st));
-    if (pf_matter_shells_device(who, task, sv.fb, mc.field, nullptr, n, sv.y0, sv.nyl, sv.nzp, 0, counters + MC_WORDS, counters, coll, &g[nbins], st)) return 1;
+    if (corr) {   // (ncells and r2sum from the separation-space pass over a field of zeros)
+      HLHIP(task, who, hipMemsetAsync(rev, 0, field_bytes, st));
+      if (pf_corr_shells_device(who, task, sv.fb, rev, n, mc.x0, cv.nxl, mc.rpitch, los, counters + MC_WORDS, coll, &g[nbins], st)) return 1;
+    } else {
+      HLHIP(task, who, hipMemsetAsync(mc.field, 0, (size_t)n * sv.nyl * sv.nzp * 2 * sv.fb, st));
+      if (pf_matter_shells_device(who, task, sv.fb, mc.field, nullptr, n, sv.y0, sv.nyl, sv.nzp, 0, counters + MC_WORDS, counters, coll, &g[nbins], st)) return 1;
+    }
     timer.mark(-1);
   }
   timer.end();
@@ -420,12 +476,22 @@ static int halo_spectra(const char *who, bool multi, pf_ctx *c, int flags, size_
     hi[k].modes = n3;
     if (!hi[k].weight_sum) {
       hi[k].empty_cells = n3;
+      if (corr) nonfinite_cells[k] = 0;
       for (size_t s = 0; s < per; s++) { power[(size_t)k * per + s] = 0.0; if (cross) cross[(size_t)k * per + s] = 0.0; }
       continue;
     }
     HLHIP(task, who, hipMemcpyAsync(slots.data(), b.words + (size_t)k * bin_words, MC_WORDS * 8, hipMemcpyDeviceToHost, st));
-    HLHIP(task, who, hipMemcpyAsync(hd.data(), g[k].out, hd.size() * 8, hipMemcpyDeviceToHost, st));
+    u64 bad_cells[2] = {0, 0};
+    if (corr) {   // xi of each field [3][nb] from the tables of its own; the cells that are not finite stand behind the limbs, summed over the ranks already
+      HLHIP(task, who, hipMemcpyAsync(hd.data(), g[k].out, per * 8, hipMemcpyDeviceToHost, st));
+      HLHIP(task, who, hipMemcpyAsync(&bad_cells[0], g[k].nm + 26 * nb, 8, hipMemcpyDeviceToHost, st));
+      if (cross) {
+        HLHIP(task, who, hipMemcpyAsync(hd.data() + per, gx[k].out, per * 8, hipMemcpyDeviceToHost, st));
+        HLHIP(task, who, hipMemcpyAsync(&bad_cells[1], gx[k].nm + 26 * nb, 8, hipMemcpyDeviceToHost, st));
+      }
+    } else HLHIP(task, who, hipMemcpyAsync(hd.data(), g[k].out, hd.size() * 8, hipMemcpyDeviceToHost, st));
     HLHIP(task, who, hipStreamSynchronize(st));
+    if (corr) nonfinite_cells[k] = bad_cells[0] + bad_cells[1];
     memcpy(power + (size_t)k * per, hd.data(), per * 8);
     if (cross) memcpy(cross + (size_t)k * per, hd.data() + per, per * 8);
     u64 *w = grid_words.data() + (size_t)k * (2 + (size_t)P);
@@ -445,11 +511,22 @@ static int halo_spectra(const char *who, bool multi, pf_ctx *c, int flags, size_
 
 extern "C" int pf_halo_power(pf_ctx *c, int flags, size_t count, const double *pos, double scale, const int *mass, int nbins, const int *mass_range,
                              unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross, pf_halo_info *info) {
-  return halo_spectra("pf_halo_power", false, c, flags, count, pos, nullptr, scale, 0.0, 0, mass, nbins, mass_range, nmodes, k2sum, power, cross, info);
+  return halo_spectra("pf_halo_power", HM_POWER, c, flags, count, pos, nullptr, scale, 0.0, 0, mass, nbins, mass_range, nmodes, k2sum, power, cross, info);
 }
 extern "C" int pf_halo_multipoles(pf_ctx *c, int flags, size_t count, const double *pos, const double *vel, double scale, double vfac, int los, const int *mass, int nbins,
                                   const int *mass_range, unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross, pf_halo_info *info) {
-  return halo_spectra("pf_halo_multipoles", true, c, flags, count, pos, vel, scale, vfac, los, mass, nbins, mass_range, nmodes, k2sum, power, cross, info);
+  return halo_spectra("pf_halo_multipoles", HM_MULTI, c, flags, count, pos, vel, scale, vfac, los, mass, nbins, mass_range, nmodes, k2sum, power, cross, info);
+}
+// info arrives as pf_corr_info: the body fills pf_halo_info of its own, so that a null info is refused where every refusal is (and told
+// to the other ranks), and nothing of the caller's is written before the call has succeeded
+extern "C" int pf_halo_correlation(pf_ctx *c, int flags, size_t count, const double *pos, const double *vel, double scale, double vfac, int los, const int *mass, int nbins,
+                                   const int *mass_range, unsigned long long *ncells, unsigned long long *r2sum, double *xi, double *xi_cross, pf_corr_info *info) {
+  pf_halo_info hinfo[PF_HALO_MAX_BINS];
+  u64 bad_cells[PF_HALO_MAX_BINS];
+  if (halo_spectra("pf_halo_correlation", HM_CORR, c, flags, count, pos, vel, scale, vfac, los, mass, nbins, mass_range, ncells, r2sum, xi, xi_cross, info ? hinfo : nullptr, bad_cells))
+    return 1;
+  for (int k = 0; k < nbins; k++) { info[k].halo = hinfo[k]; info[k].cells = hinfo[k].modes; info[k].nonfinite_cells = bad_cells[k]; }
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------ tap ----

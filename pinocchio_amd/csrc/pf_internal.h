@@ -403,6 +403,21 @@ int pf_matter_shells_device(const char *who, int task, int fb, const void *spec_
 size_t pf_multipole_shells_words(int n, int P);
 int pf_multipole_shells_device(const char *who, int task, int fb, const void *spec_m, const void *spec_lin, int n, int y0, int nyl, long long pitch, int flags, int los,
                                unsigned long long *words, unsigned long long *counters, pf_ctx *coll, PfShellSums *sums, hipStream_t st);
+// ---- the two passes of pf_halo_correlation (pf_power.hip; pf_halo.hip calls them; pf_corr_core.h) ----
+// the form pass on the rows y0 .. y0 + nyl - 1 of spec_m: out = ((F)(t / N^3), 0) per stored mode, t the auto term of matter_terms
+// (which 0; spec_lin is not read) or its cross term with spec_lin (which 1), deconvolved by the table C (null: not; on the device,
+// n/2 + 1 doubles: pf_corr_deconv_upload).  out may be spec_m: a mode is read and written by one lane.  The k = 0 mode is written as
+// zero; so is a term that is not finite, which adds its weight to MC_NONFIN_MODES of `counters`.  Nothing is synchronised
+int pf_corr_deconv_upload(const char *who, int task, int flags, int n, double *Cdev, const double **C, hipStream_t st);
+int pf_corr_form_device(const char *who, int task, int fb, const void *spec_m, const void *spec_lin, void *out, int n, int y0, int nyl, long long pitch, const double *C,
+                        int which, unsigned long long *counters, hipStream_t st);
+// the shell sums of a real field in separation space, the planes x0 .. x0 + nxl - 1 of the box in rows of `pitch` reals: six positive
+// sums per shell (pf_corr_core.h) -> this slab's sums on the device, or with coll (collective) the box's on every rank: nm ([nb]
+// ncells, [nb] r2sum, then the limbs, then at nm[26 nb] the cells that are not finite) and out ([3][nb] xi = positive - negative,
+// [6][nb] the positive sums).  words: pf_corr_shells_words(n, ranks of coll), not yet cleared.  Nothing is synchronised
+size_t pf_corr_shells_words(int n, int P);
+int pf_corr_shells_device(const char *who, int task, int fb, const void *real, int n, int x0, int nxl, long long pitch, int los, unsigned long long *words, pf_ctx *coll,
+                          PfShellSums *sums, hipStream_t st);
 // counters of a pf_matter call on the device: PF_MATTER_SLOTS copies of each, a workgroup adds to the copy of its index -- one counter for all
 // wavefronts of a 1024^3 call is 1.7e7 atomics on one address: the contrast pass took 778 ms that way and takes 8 (profiles/matter_notes.md);
 // the copies are summed (MC_MAX: reduced) on the host.  The scans of pf_matter_shells_device add to MC_NONFIN_MODES of `counters`
@@ -416,6 +431,11 @@ struct PfMatterCtx { void *field; long long rpitch; int x0, lpt_order; };
 void pf_ctx_matter_view(pf_ctx *c, PfMatterCtx *m);
 int pf_ctx_matter_forward(pf_ctx *c);                 // the context's forward transform of that field, in place
 int pf_ctx_matter_export(pf_ctx *c, double *host);    // its real rows -> [nxl][n][n] fp64 on the host (through the staging fields)
+// the field the context's reverse transform works on in place (the field of pf_reverse_transform: A[0]; with one rank that is
+// `field` above) and its bytes; the transform itself, spectrum -> real rows of rpitch reals times 1 / N^3.  With more than one rank
+// it receives into receive field 0: `field` above is overwritten
+void *pf_ctx_matter_reverse_field(pf_ctx *c, size_t *bytes);
+int pf_ctx_matter_reverse(pf_ctx *c);
 int pf_launch_block_vec3(const float *vel12, size_t ncell, int o, size_t first, size_t count, float *out, hipStream_t st);
 int pf_launch_block_id(int id_bytes, unsigned long long global_first, size_t count, void *out, hipStream_t st);
 int pf_launch_to_blocks(int field_bytes, const void *src, void *dst, int nxl, int n, int nyl, int nzp, int back, hipStream_t st);

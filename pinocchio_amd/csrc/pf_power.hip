@@ -53,7 +53,8 @@
 #include <vector>
 
 #include "pf_internal.h"
-#include "pf_multipole_core.h"   // the Legendre weights of a mode; it includes pf_matter_core.h (the two terms of a mode of two spectra) and pf_power_core.h
+#include "pf_corr_core.h"        // one cell of the separation-space pass; it includes pf_multipole_core.h (the Legendre weights of a mode), which includes
+                                 // pf_matter_core.h (the two terms of a mode of two spectra) and pf_power_core.h
 
 #define PWHIP(task, who, call)                                                                                         \
   do {                                                                                                                 \
@@ -511,6 +512,138 @@ __global__ void __launch_bounds__(PF_POWER_BLOCK) k_matter_slot_max(const u64 *s
   out[i] = m;
 }
 
+// ---- the two passes of pf_halo_correlation (pf_corr_core.h).  The form pass: on the rows of matter_walk every stored mode of spec
+// becomes ((F)(t / N^3), 0), t its auto term (which 0) or its cross term with v.lin (which 1), where it stood or in another field of
+// the same layout: a mode is read and written by the one lane that owns it.  A term that is not finite is written as zero and
+// counted with its weight; the k = 0 mode is written as zero
+template <class F>
+__global__ void __launch_bounds__(PF_POWER_BLOCK) k_corr_form(MatterView v, void *out, int which, double n3, u64 *counters) {
+  const unsigned int r0 = blockIdx.x * v.rows_per_wg, r1 = r0 + v.rows_per_wg < v.rows ? r0 + v.rows_per_wg : v.rows;
+  const unsigned int half = (unsigned int)v.n / 2;
+  u64 nonfin = 0;
+  for (unsigned int row = r0; row < r1; row++) {
+    const unsigned int kx = row / (unsigned int)v.nyl, yl = row - kx * (unsigned int)v.nyl;
+    const int sx = pf_power_signed((int)kx, v.n), sy = pf_power_signed((int)yl + v.y0, v.n);
+    const unsigned int kxy2 = (unsigned int)(sx * sx + sy * sy);
+    const double cxy = v.C ? v.C[power_abs(sx)] * v.C[power_abs(sy)] : 1.0;
+    for (unsigned int kz = threadIdx.x; kz <= half; kz += PF_POWER_BLOCK) {
+      bool fin, bad;
+      double ta, tc;
+      matter_terms<F>(v, row, kz, cxy, ta, tc, fin);
+      const double q = pf_corr_form(which ? tc : ta, kxy2 + kz * kz, n3, &bad);
+      if (bad) nonfin += (kz > 0 && kz < half) ? 2u : 1u;
+      F *e = (F *)out + 2 * ((long long)row * v.pitch + kz);
+      if constexpr (sizeof(F) == 8) *(double2 *)e = make_double2(q, 0.0);
+      else *(float2 *)e = make_float2((float)q, 0.0f);
+    }
+  }
+  nonfin = power_wave_sum(nonfin);
+  if (nonfin && (threadIdx.x & (warpSize - 1)) == 0) atomicAdd(counters + (size_t)(blockIdx.x % PF_MATTER_SLOTS) * MC_COUNT + MC_NONFIN_MODES, nonfin);
+}
+
+// The shell pass in separation space: a real field, the planes [x0, x0 + nxl) of the box in rows (x_local, y) of `pitch` reals of which
+// the first n are cells.  The same two passes and the same fixed point as above on a walk of its own (corr_walk: workgroup g takes
+// the rows [g rpw, (g + 1) rpw), thread t the cells z = t, t + 256, ... < n); six positive sums per shell, a launch carries the sums
+// [first, first + ns).  Tables: smax [6][nb], nm [nb], k2 [nb], pl [6][4 nb], nonfin [1]
+struct CorrView { const void *real; int n, nxl, x0, los; long long pitch; unsigned int rows, rows_per_wg; };
+struct CorrTabs { u64 *smax, *nm, *k2, *pl, *nonfin; double *out; };
+
+template <class F, class OP> __device__ __forceinline__ void corr_walk(const CorrView &v, OP op) {
+  const unsigned int r0 = blockIdx.x * v.rows_per_wg, r1 = r0 + v.rows_per_wg < v.rows ? r0 + v.rows_per_wg : v.rows;
+  for (unsigned int row = r0; row < r1; row++) {
+    const unsigned int xl = row / (unsigned int)v.n, y = row - xl * (unsigned int)v.n;
+    const int sx = pf_power_signed((int)xl + v.x0, v.n), sy = pf_power_signed((int)y, v.n);
+    const F *line = (const F *)v.real + (long long)row * v.pitch;
+    for (unsigned int z = threadIdx.x; z < (unsigned int)v.n; z += PF_POWER_BLOCK) {
+      const int sz = pf_power_signed((int)z, v.n);
+      const unsigned int r2 = pf_corr_r2(sx, sy, sz);
+      op(pf_power_shell(r2), r2, pf_corr_a(v.los, sx, sy, sz), (double)line[z]);
+    }
+  }
+}
+
+// ncells, r2sum and the cells that are not finite are counted by the launch that carries sum 0
+template <class F>
+__global__ void __launch_bounds__(PF_POWER_BLOCK) k_corr_scan(CorrView v, int first, int ns, int nb, CorrTabs g) {
+  extern __shared__ u64 lds[];
+  u64 *smax = lds, *snm = lds + (size_t)ns * nb, *sk2 = snm + nb;
+  for (int k = threadIdx.x; k < (ns + 2) * nb; k += PF_POWER_BLOCK) lds[k] = 0;
+  __syncthreads();
+  const bool count = first == 0;
+  u64 nonfin = 0;
+  corr_walk<F>(v, [&](int b, unsigned int r2, unsigned int a, double val) {
+    const bool fin = pf_power_finite(val);
+    if (count) {
+      atomicAdd(&snm[b], (u64)1);
+      if (r2) atomicAdd(&sk2[b], (u64)r2);
+      if (!fin) nonfin++;
+    }
+    if (!fin) return;
+    double L2, L4, x[PF_CORR_NORDERS];
+    pf_multipole_weights(a, r2, &L2, &L4);
+    pf_corr_terms(val, L2, L4, x);
+#pragma unroll
+    for (int k = 0; k < PF_CORR_NORDERS; k++) {
+      const double t = fabs(x[k]);
+      const int s = pf_corr_sum_of(k, x[k]) - first;
+      if (t > 0.0 && s >= 0 && s < ns) power_max_lds(&smax[s * nb + b], (u64)__double_as_longlong(t));
+    }
+  });
+  nonfin = power_wave_sum(nonfin);
+  if (nonfin && (threadIdx.x & (warpSize - 1)) == 0) atomicAdd(g.nonfin, nonfin);
+  __syncthreads();
+  for (int b = threadIdx.x; b < nb; b += PF_POWER_BLOCK) {
+    if (count && snm[b]) { atomicAdd(&g.nm[b], snm[b]); atomicAdd(&g.k2[b], sk2[b]); }
+    for (int s = 0; s < ns; s++)
+      if (smax[s * nb + b]) atomicMax(&g.smax[(size_t)(first + s) * nb + b], smax[s * nb + b]);
+  }
+}
+
+template <class F>
+__global__ void __launch_bounds__(PF_POWER_BLOCK) k_corr_acc(CorrView v, int first, int ns, int nb, CorrTabs g) {
+  extern __shared__ u64 lds[];
+  u64 *sp = lds;
+  int *se = (int *)(lds + (size_t)3 * ns * nb);
+  for (int k = threadIdx.x; k < 3 * ns * nb; k += PF_POWER_BLOCK) lds[k] = 0;
+  for (int k = threadIdx.x; k < ns * nb; k += PF_POWER_BLOCK) se[k] = power_exponent_of(g.smax[(size_t)first * nb + k]);
+  __syncthreads();
+  corr_walk<F>(v, [&](int b, unsigned int r2, unsigned int a, double val) {
+    if (!pf_power_finite(val)) return;
+    double L2, L4, x[PF_CORR_NORDERS];
+    pf_multipole_weights(a, r2, &L2, &L4);
+    pf_corr_terms(val, L2, L4, x);
+#pragma unroll
+    for (int k = 0; k < PF_CORR_NORDERS; k++) {
+      const double t = fabs(x[k]);
+      const int s = pf_corr_sum_of(k, x[k]) - first;
+      if (!(t > 0.0) || s < 0 || s >= ns) continue;
+      uint32_t l[3];
+      pf_power_limbs(t, se[s * nb + b], l);
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+        if (l[i]) atomicAdd(&sp[3 * (s * nb + b) + i], (u64)l[i]);
+    }
+  });
+  __syncthreads();
+  for (int k = threadIdx.x; k < ns * nb; k += PF_POWER_BLOCK) power_flush(sp + 3 * k, g.pl + 4 * ((size_t)first * nb + k));
+}
+
+// out: [3][nb] xi (l = 0, 2, 4: positive - negative, formed once), then [6][nb] the positive sums themselves
+__global__ void __launch_bounds__(PF_POWER_BLOCK) k_corr_final(int nb, CorrTabs g) {
+  const int b = blockIdx.x * PF_POWER_BLOCK + threadIdx.x;
+  if (b >= nb) return;
+  double s[PF_CORR_NSUMS];
+  double *parts = g.out + PF_CORR_NORDERS * (size_t)nb;
+#pragma unroll
+  for (int which = 0; which < PF_CORR_NSUMS; which++) {
+    const u64 mx = g.smax[(size_t)which * nb + b];
+    s[which] = mx ? pf_power_from_limbs(g.pl + 4 * ((size_t)which * nb + b), 4, power_exponent_of(mx)) : 0.0;
+    parts[(size_t)which * nb + b] = s[which];
+  }
+#pragma unroll
+  for (int l = 0; l < PF_CORR_NORDERS; l++) g.out[(size_t)l * nb + b] = s[2 * l] - s[2 * l + 1];
+}
+
 // ------------------------------------------------------------------------------------------------------------ launches ----
 // PF_POWER_TIMES=1: device ms of the last call, from the clearing of the tables (the upload of the window tables included) to the finishing kernel (profiles/tools/power_time.py)
 static double power_last_ms = 0.0;
@@ -800,6 +933,151 @@ extern "C" int pf_debug_multipole_shells(int field_bytes, int n, int y0, int nyl
   memset(info, 0, sizeof(*info));
   info->modes = (u64)nyl * n * n;
   for (int k = 0; k < PF_MATTER_SLOTS; k++) info->nonfinite_modes += slots[(size_t)k * MC_COUNT + MC_NONFIN_MODES];
+  return 0;
+}
+
+// ---- the passes of pf_halo_correlation (pf_internal.h; pf_halo.hip calls them) ----
+static_assert(PF_CORR_NORDERS == PF_CORR_ORDERS && 2 * PF_CORR_NSUMS == PF_CORR_SUMS, "pf_corr_core.h and pinfmax.h disagree");
+int pf_corr_deconv_upload(const char *who, int task, int flags, int n, double *Cdev, const double **C, hipStream_t st) {
+  return matter_deconv_upload(who, task, flags, n, Cdev, C, st);
+}
+int pf_corr_form_device(const char *who, int task, int fb, const void *spec_m, const void *spec_lin, void *out, int n, int y0, int nyl, long long pitch, const double *C,
+                        int which, u64 *counters, hipStream_t st) {
+  MatterView v;
+  unsigned int nwg;
+  if (which < 0 || which > 1) return pf_fail(task, "%s: form %d (0 auto, 1 cross)", who, which);
+  if (which && !spec_lin) return pf_fail(task, "%s: the cross form without a second spectrum", who);
+  if (power_view(who, task, "a", spec_m, which ? spec_lin : nullptr, n, y0, nyl, pitch, PF_POWER_MAXWG_SHELLS, 0, &v, &nwg)) return 1;
+  if ((uintptr_t)out & 15) return pf_fail(task, "%s: the formed spectrum is not 16-byte aligned (internal error)", who);
+  v.lin = which ? spec_lin : nullptr; v.C = C; v.los = 0;
+  const double n3 = (double)n * (double)n * (double)n;
+  hipLaunchKernelGGL(fb == 8 ? k_corr_form<double> : k_corr_form<float>, dim3(nwg), dim3(PF_POWER_BLOCK), 0, st, v, out, which, n3, counters);
+  if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+  return 0;
+}
+
+// Six positive sums per shell.  Words: smax [6 nb], nm [nb], k2 [nb], pl [24 nb], nonfin [1]; then out [9 nb] doubles (3 nb xi, 6 nb
+// the positive sums); with P ranks the slots of the scans' maxima behind them, [P][6 nb].  A launch carries as many sums as
+// PF_CORR_LDS_SCAN / _ACC bytes of LDS hold, as the multipole passes do, in runs of an even length where there is room for two, so
+// that the two sums of a term's signs ride together.  PF_CORR_SCAN_EACH=1 (tests only): one sum per launch
+#ifndef PF_CORR_LDS_SCAN
+#define PF_CORR_LDS_SCAN PF_POWER_LDS_MAX
+#endif
+#ifndef PF_CORR_LDS_ACC
+#define PF_CORR_LDS_ACC PF_POWER_LDS_MAX
+#endif
+static int corr_group(size_t room) {
+  int g = room < 1 ? 1 : room > (size_t)PF_CORR_NSUMS ? PF_CORR_NSUMS : (int)room;
+  if (g > 1) g &= ~1;
+  const int launches = (PF_CORR_NSUMS + g - 1) / g;
+  int per = (PF_CORR_NSUMS + launches - 1) / launches;
+  if (per > 1 && (per & 1)) per++;   // (still at most g, which is even)
+  return per;
+}
+size_t pf_corr_shells_words(int n, int P) {
+  const size_t nb = (size_t)pf_power_nbins(n);
+  return 41 * nb + 1 + (P > 1 ? (size_t)P * PF_CORR_NSUMS * nb : 0);
+}
+int pf_corr_shells_device(const char *who, int task, int fb, const void *real, int n, int x0, int nxl, long long pitch, int los, u64 *words, pf_ctx *coll, PfShellSums *sums,
+                          hipStream_t st) {
+  const int nb = pf_power_nbins(n);
+  const char *each = getenv("PF_CORR_SCAN_EACH");
+  const bool one = each && atoi(each) != 0;
+  const size_t table = (size_t)nb * 8, acc1 = (size_t)nb * 28;
+  const int per_scan = corr_group(one ? 1 : PF_CORR_LDS_SCAN / table < 3 ? 1 : PF_CORR_LDS_SCAN / table - 2), per_acc = corr_group(one ? 1 : PF_CORR_LDS_ACC / acc1);
+  const size_t lds_scan = (size_t)(per_scan + 2) * table, lds_acc = (size_t)per_acc * acc1;
+  if (lds_scan > PF_POWER_LDS_MAX || lds_acc > PF_POWER_LDS_MAX) return pf_fail(task, "%s: the %d shells of a grid of %d do not fit the LDS tables", who, nb, n);
+  if (los < 0 || los > 2) return pf_fail(task, "%s: a line of sight along axis %d (0, 1 or 2)", who, los);
+  if (n < 2 || n > 2048 || x0 < 0 || nxl < 1 || x0 + nxl > n || pitch < n) return pf_fail(task, "%s: planes %d .. %d of a grid of %d in rows of %lld (internal error)", who, x0, x0 + nxl - 1, n, pitch);
+  CorrView v;
+  v.real = real; v.n = n; v.nxl = nxl; v.x0 = x0; v.los = los; v.pitch = pitch;
+  v.rows = (unsigned int)nxl * (unsigned int)n;
+  v.rows_per_wg = (v.rows + PF_POWER_MAXWG_SHELLS - 1) / PF_POWER_MAXWG_SHELLS;
+  const unsigned int nwg = (v.rows + v.rows_per_wg - 1) / v.rows_per_wg;
+  PWHIP(task, who, hipMemsetAsync(words, 0, (41 * (size_t)nb + 1) * 8, st));
+  CorrTabs g;
+  g.smax = words; g.nm = g.smax + PF_CORR_NSUMS * (size_t)nb; g.k2 = g.nm + nb; g.pl = g.k2 + nb; g.nonfin = g.pl + 4 * PF_CORR_NSUMS * (size_t)nb;
+  g.out = (double *)(g.nonfin + 1);
+  const dim3 gr(nwg), bl(PF_POWER_BLOCK);
+  int scans = 0;
+  for (int first = 0; first < PF_CORR_NSUMS; first += per_scan, scans++) {
+    const int ns = first + per_scan < PF_CORR_NSUMS ? per_scan : PF_CORR_NSUMS - first;
+    hipLaunchKernelGGL(fb == 8 ? k_corr_scan<double> : k_corr_scan<float>, gr, bl, lds_scan, st, v, first, ns, nb, g);
+    if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+  }
+  // more than one rank: the maxima of the box before any limb is formed, as in pf_matter_shells_device
+  if (coll && matter_box_max(who, task, coll, g.smax, (size_t)PF_CORR_NSUMS * nb, words + 41 * (size_t)nb + 1, st)) return 1;
+  for (int first = 0; first < PF_CORR_NSUMS; first += per_acc) {
+    const int ns = first + per_acc < PF_CORR_NSUMS ? per_acc : PF_CORR_NSUMS - first;
+    hipLaunchKernelGGL(fb == 8 ? k_corr_acc<double> : k_corr_acc<float>, gr, bl, lds_acc, st, v, first, ns, nb, g);
+    if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+  }
+  if (coll && pf_ctx_allreduce(coll, g.nm, (size_t)(2 + 4 * PF_CORR_NSUMS) * nb + 1, 1)) return 1;   // nm, k2, the limbs pl and nonfin lie one behind the other
+  hipLaunchKernelGGL(k_corr_final, dim3((unsigned int)((nb + PF_POWER_BLOCK - 1) / PF_POWER_BLOCK)), bl, 0, st, nb, g);
+  if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
+  sums->nm = g.nm; sums->out = g.out; sums->scans = scans;
+  return 0;
+}
+
+extern "C" int pf_debug_corr_form(int field_bytes, int n, int y0, int nyl, const double *spec_m, const double *spec_lin, int flags, int which, double *spec_out,
+                                  pf_matter_info *info) {
+  const char *who = "pf_debug_corr_form";
+  if (!spec_m || !spec_out || !info) return pf_fail(0, "%s: null argument", who);
+  if (flags & ~(PF_MATTER_NGP | PF_MATTER_DECONVOLVE)) return pf_fail(0, "%s: unknown flag bits 0x%x", who, (unsigned int)(flags & ~(PF_MATTER_NGP | PF_MATTER_DECONVOLVE)));
+  if (which < 0 || which > 1) return pf_fail(0, "%s: form %d (0 auto, 1 cross)", who, which);
+  if (which && !spec_lin) return pf_fail(0, "%s: the cross form without a second spectrum", who);
+  const size_t slot_words = (size_t)PF_MATTER_SLOTS * MC_COUNT;
+  PfSpecStage d = {};
+  if (pf_stage_spectra(who, field_bytes, n, y0, nyl, 2, spec_m, which ? spec_lin : nullptr, slot_words + (size_t)(n / 2 + 1), &d)) return 1;
+  PWHIP(0, who, hipMemsetAsync(d.words, 0, slot_words * 8, nullptr));
+  const double *Ctab = nullptr;
+  if (matter_deconv_upload(who, 0, flags, n, (double *)(d.words + slot_words), &Ctab, nullptr)) return 1;
+  if (pf_corr_form_device(who, 0, field_bytes, d.spec[0], which ? d.spec[1] : nullptr, d.spec[0], n, y0, nyl, d.nzp, Ctab, which, d.words, nullptr)) return 1;
+  const int nzh = n / 2 + 1;
+  if (pf_launch_spec_export_t(field_bytes, d.spec[0], (double *)d.in, n, nyl, nzh, d.nzp, nullptr)) return pf_fail(0, "%s: launch failed", who);
+  std::vector<u64> slots(slot_words);
+  PWHIP(0, who, hipMemcpyAsync(spec_out, d.in, (size_t)nyl * n * nzh * 16, hipMemcpyDeviceToHost, nullptr));
+  PWHIP(0, who, hipMemcpyAsync(slots.data(), d.words, slot_words * 8, hipMemcpyDeviceToHost, nullptr));
+  PWHIP(0, who, hipStreamSynchronize(nullptr));
+  memset(info, 0, sizeof(*info));
+  info->modes = (u64)nyl * n * n;
+  for (int k = 0; k < PF_MATTER_SLOTS; k++) info->nonfinite_modes += slots[(size_t)k * MC_COUNT + MC_NONFIN_MODES];
+  return 0;
+}
+
+struct CorrStage { void *in, *field; u64 *words; ~CorrStage() { hipFree(in); hipFree(field); hipFree(words); } };
+extern "C" int pf_debug_corr_shells(int field_bytes, int n, int x0, int nxl, const double *real_host, int los, unsigned long long *ncells, unsigned long long *r2sum, double *xi,
+                                    double *parts, unsigned long long *nonfinite_cells) {
+  const char *who = "pf_debug_corr_shells";
+  if (!real_host || !ncells || !r2sum || !xi || !nonfinite_cells) return pf_fail(0, "%s: null argument", who);
+  if (field_bytes != 4 && field_bytes != 8) return pf_fail(0, "%s: fields of %d bytes (4 or 8)", who, field_bytes);
+  if (n < 2 || n > 2048 || (n & 1)) return pf_fail(0, "%s: a grid of %d (even, 2 to 2048)", who, n);
+  if (x0 < 0 || nxl < 1 || x0 + nxl > n) return pf_fail(0, "%s: planes %d .. %d leave the grid of %d", who, x0, x0 + nxl - 1, n);
+  if (los < 0 || los > 2) return pf_fail(0, "%s: a line of sight along axis %d (0, 1 or 2)", who, los);
+  // the production layout of a real field: rows of 2 (n/2 + 64 / field_bytes) reals, NaN patterns in the padding that no sum may see
+  const long long pitch = 2 * ((long long)n / 2 + 64 / field_bytes), nrows = (long long)nxl * n;
+  const size_t in_bytes = (size_t)nrows * n * 8, field = (size_t)nrows * pitch * field_bytes, words = pf_corr_shells_words(n, 1);
+  CorrStage d = {nullptr, nullptr, nullptr};
+  if (hipMalloc(&d.in, in_bytes) != hipSuccess || hipMalloc(&d.field, field) != hipSuccess || hipMalloc((void **)&d.words, words * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    return pf_fail(0, "%s: cannot allocate %zu bytes on the device", who, in_bytes + field + words * 8);
+  }
+  PWHIP(0, who, hipMemset(d.field, 0xff, field));
+  PWHIP(0, who, hipMemcpy(d.in, real_host, in_bytes, hipMemcpyHostToDevice));
+  if (pf_launch_real_import(field_bytes, (const double *)d.in, d.field, nrows, n, pitch, nullptr)) return pf_fail(0, "%s: launch failed", who);
+  PfShellSums g;
+  if (pf_corr_shells_device(who, 0, field_bytes, d.field, n, x0, nxl, pitch, los, d.words, nullptr, &g, nullptr)) return 1;
+  const size_t nb = (size_t)pf_power_nbins(n);
+  std::vector<u64> hu(26 * nb + 1);
+  std::vector<double> hd(9 * nb);
+  PWHIP(0, who, hipMemcpyAsync(hu.data(), g.nm, hu.size() * 8, hipMemcpyDeviceToHost, nullptr));
+  PWHIP(0, who, hipMemcpyAsync(hd.data(), g.out, hd.size() * 8, hipMemcpyDeviceToHost, nullptr));
+  PWHIP(0, who, hipStreamSynchronize(nullptr));
+  memcpy(ncells, hu.data(), nb * 8);
+  memcpy(r2sum, hu.data() + nb, nb * 8);
+  memcpy(xi, hd.data(), 3 * nb * 8);
+  if (parts) memcpy(parts, hd.data() + 3 * nb, PF_CORR_NSUMS * nb * 8);
+  *nonfinite_cells = hu[26 * nb];
   return 0;
 }
 
