@@ -1291,6 +1291,8 @@ int pf_debug_multipole_form(int *form);
    pf_debug_corr_shells: test tap without a context: the production shell passes on the planes x0 .. x0 + nxl - 1 of the caller's
      fp64 real field [nxl][n][n], converted to field_bytes on the way in -> ncells, r2sum, xi[3][nb], parts[6][nb] (the positive
      sums; may be NULL) and the cells that are not finite.
+   pf_debug_corr_passes: passes[0] = scans, passes[1] = accumulation passes launched by the calling thread's last separation-space
+     shell pass (0: none yet), as pf_debug_multipole_form tells them of the multipole passes.
    pf_debug_corr_times: with PF_CORR_TIMES=1 in the environment, ms[0..5] = device ms of the selection, the deposits, the contrasts,
      the transforms (forward and reverse), the form passes and the shell passes of the calling thread's last pf_halo_correlation,
      summed over its bins; 0 otherwise. */
@@ -1306,6 +1308,7 @@ int pf_debug_corr_form(int field_bytes, int n, int y0, int nyl, const double *sp
 int pf_debug_corr_shells(int field_bytes, int n, int x0, int nxl, const double *real_host, int los,
                          unsigned long long *ncells, unsigned long long *r2sum,
                          double *xi, double *parts, unsigned long long *nonfinite_cells);
+int pf_debug_corr_passes(int *passes);
 int pf_debug_corr_times(double *ms);   /* PF_CORR_TIMES=1: select, deposit, contrast, transforms (forward and reverse), form, shells */
 
 /* --- measurement --- */

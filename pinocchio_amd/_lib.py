@@ -353,6 +353,7 @@ PROTOTYPES = {
     "pf_debug_corr_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.POINTER(MatterInfo)]),
     "pf_debug_corr_shells": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _dp, _dp,
                                        C.POINTER(C.c_ulonglong)]),
+    "pf_debug_corr_passes": (C.c_int, [C.POINTER(C.c_int)]),
     "pf_debug_corr_times": (C.c_int, [_dp]),
     "pf_get_cputime": (C.c_int, [_vp, C.POINTER(CpuTime)]),
     "pf_reset_cputime": (C.c_int, [_vp]),

@@ -325,6 +325,14 @@ def debug_corr_times():
     return tuple(float(x) for x in ms)
 
 
+def corr_passes():
+    """what the calling thread's last separation-space shell pass launched: (scans, accumulation passes); zeros for none yet
+    (pf_debug_corr_passes)"""
+    passes = (C.c_int * 2)()
+    _lib.load().pf_debug_corr_passes(passes)
+    return int(passes[0]), int(passes[1])
+
+
 def debug_corr_form(spec_m, spec_lin=None, y0: int = 0, field_bytes: int = 8, ngp: bool = False, deconvolve: bool = False, which: int = 0):
     """the production form pass of halo_correlation on the rows y0 .. y0 + nyl - 1 of a ky-slab [nyl][n (kx)][n/2+1] complex128
     (pf_debug_corr_form): which 0 -> |m|^2 / N^3, which 1 -> Re(m conj lin) / N^3 (needs spec_lin), deconvolved or not, rounded once to

@@ -414,7 +414,8 @@ int pf_corr_form_device(const char *who, int task, int fb, const void *spec_m, c
 // the shell sums of a real field in separation space, the planes x0 .. x0 + nxl - 1 of the box in rows of `pitch` reals: six positive
 // sums per shell (pf_corr_core.h) -> this slab's sums on the device, or with coll (collective) the box's on every rank: nm ([nb]
 // ncells, [nb] r2sum, then the limbs, then at nm[26 nb] the cells that are not finite) and out ([3][nb] xi = positive - negative,
-// [6][nb] the positive sums).  words: pf_corr_shells_words(n, ranks of coll), not yet cleared.  Nothing is synchronised
+// [6][nb] the positive sums).  words: pf_corr_shells_words(n, ranks of coll), not yet cleared.  Nothing is synchronised.  What was
+// launched is also kept for pf_debug_corr_passes
 size_t pf_corr_shells_words(int n, int P);
 int pf_corr_shells_device(const char *who, int task, int fb, const void *real, int n, int x0, int nxl, long long pitch, int los, unsigned long long *words, pf_ctx *coll,
                           PfShellSums *sums, hipStream_t st);

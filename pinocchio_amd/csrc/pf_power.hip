@@ -959,13 +959,20 @@ int pf_corr_form_device(const char *who, int task, int fb, const void *spec_m, c
 // Six positive sums per shell.  Words: smax [6 nb], nm [nb], k2 [nb], pl [24 nb], nonfin [1]; then out [9 nb] doubles (3 nb xi, 6 nb
 // the positive sums); with P ranks the slots of the scans' maxima behind them, [P][6 nb].  A launch carries as many sums as
 // PF_CORR_LDS_SCAN / _ACC bytes of LDS hold, as the multipole passes do, in runs of an even length where there is room for two, so
-// that the two sums of a term's signs ride together.  PF_CORR_SCAN_EACH=1 (tests only): one sum per launch
+// that the two sums of a term's signs ride together.  PF_CORR_SCAN_EACH=1 (tests only): one sum per launch.  What was launched is kept
+// for pf_debug_corr_passes
 #ifndef PF_CORR_LDS_SCAN
 #define PF_CORR_LDS_SCAN PF_POWER_LDS_MAX
 #endif
 #ifndef PF_CORR_LDS_ACC
 #define PF_CORR_LDS_ACC PF_POWER_LDS_MAX
 #endif
+static thread_local int corr_last_passes[2] = {0, 0};   // scans and accumulations launched by the last call
+extern "C" int pf_debug_corr_passes(int *passes) {
+  if (!passes) return 1;
+  passes[0] = corr_last_passes[0]; passes[1] = corr_last_passes[1];
+  return 0;
+}
 static int corr_group(size_t room) {
   int g = room < 1 ? 1 : room > (size_t)PF_CORR_NSUMS ? PF_CORR_NSUMS : (int)room;
   if (g > 1) g &= ~1;
@@ -999,7 +1006,7 @@ int pf_corr_shells_device(const char *who, int task, int fb, const void *real, i
   g.smax = words; g.nm = g.smax + PF_CORR_NSUMS * (size_t)nb; g.k2 = g.nm + nb; g.pl = g.k2 + nb; g.nonfin = g.pl + 4 * PF_CORR_NSUMS * (size_t)nb;
   g.out = (double *)(g.nonfin + 1);
   const dim3 gr(nwg), bl(PF_POWER_BLOCK);
-  int scans = 0;
+  int scans = 0, accs = 0;
   for (int first = 0; first < PF_CORR_NSUMS; first += per_scan, scans++) {
     const int ns = first + per_scan < PF_CORR_NSUMS ? per_scan : PF_CORR_NSUMS - first;
     hipLaunchKernelGGL(fb == 8 ? k_corr_scan<double> : k_corr_scan<float>, gr, bl, lds_scan, st, v, first, ns, nb, g);
@@ -1007,7 +1014,7 @@ int pf_corr_shells_device(const char *who, int task, int fb, const void *real, i
   }
   // more than one rank: the maxima of the box before any limb is formed, as in pf_matter_shells_device
   if (coll && matter_box_max(who, task, coll, g.smax, (size_t)PF_CORR_NSUMS * nb, words + 41 * (size_t)nb + 1, st)) return 1;
-  for (int first = 0; first < PF_CORR_NSUMS; first += per_acc) {
+  for (int first = 0; first < PF_CORR_NSUMS; first += per_acc, accs++) {
     const int ns = first + per_acc < PF_CORR_NSUMS ? per_acc : PF_CORR_NSUMS - first;
     hipLaunchKernelGGL(fb == 8 ? k_corr_acc<double> : k_corr_acc<float>, gr, bl, lds_acc, st, v, first, ns, nb, g);
     if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
@@ -1016,6 +1023,7 @@ int pf_corr_shells_device(const char *who, int task, int fb, const void *real, i
   hipLaunchKernelGGL(k_corr_final, dim3((unsigned int)((nb + PF_POWER_BLOCK - 1) / PF_POWER_BLOCK)), bl, 0, st, nb, g);
   if (hipGetLastError() != hipSuccess) return pf_fail(task, "%s: launch failed", who);
   sums->nm = g.nm; sums->out = g.out; sums->scans = scans;
+  corr_last_passes[0] = scans; corr_last_passes[1] = accs;
   return 0;
 }
 

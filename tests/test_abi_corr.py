@@ -18,6 +18,7 @@ DECLARED = {
     "pf_debug_corr_shells": "int field_bytes, int n, int x0, int nxl, const double *real_host, int los, unsigned long long *ncells, unsigned long long *r2sum, double *xi, "
                             "double *parts, unsigned long long *nonfinite_cells",
     "pf_debug_corr_times": "double *ms",
+    "pf_debug_corr_passes": "int *passes",
 }
 # what the issue forbids to touch
 UNCHANGED = {
@@ -87,10 +88,11 @@ def test_api_py_mirrors_them(lib):
     assert list(inspect.signature(api.debug_corr_form).parameters) == ["spec_m", "spec_lin", "y0", "field_bytes", "ngp", "deconvolve", "which"]
     assert list(inspect.signature(api.debug_corr_shells).parameters) == ["real", "x0", "field_bytes", "los"]
     for meth, call in ((api.Fmax.halo_correlation, "pf_halo_correlation"), (api.debug_corr_form, "pf_debug_corr_form"), (api.debug_corr_shells, "pf_debug_corr_shells"),
-                       (api.debug_corr_times, "pf_debug_corr_times")):
+                       (api.debug_corr_times, "pf_debug_corr_times"), (api.corr_passes, "pf_debug_corr_passes")):
         assert "." + call + "(" in inspect.getsource(meth), call
     assert (api.CORR_ORDERS, api.CORR_SUMS) == (3, 12) and len(api.CORR_TIME_KEYS) == 6
     assert api.debug_corr_times() == (0.0,) * 6                              # no call of this thread yet
+    assert api.corr_passes() == (0, 0)                                       # nothing launched by this thread yet
     with pytest.raises(ValueError):
         api.debug_corr_form([[[1.0, 2.0]]])
     with pytest.raises(ValueError):
@@ -130,3 +132,4 @@ def test_refusals_that_need_no_device(lib, capfd):
         assert "ERROR on task 0: pf_" in capfd.readouterr().out
         assert info.cells == 0xABCDEF and minfo.modes == 0xABCDEF and bad.value == 0xABCDEF and not any(xi[:8]) and not any(nc[:8])
     assert L.pf_debug_corr_times(None) != 0
+    assert L.pf_debug_corr_passes(None) != 0
