@@ -1311,6 +1311,68 @@ int pf_debug_corr_shells(int field_bytes, int n, int x0, int nxl, const double *
 int pf_debug_corr_passes(int *passes);
 int pf_debug_corr_times(double *ms);   /* PF_CORR_TIMES=1: select, deposit, contrast, transforms (forward and reverse), form, shells */
 
+/* --- bispectrum of the haloes: pf_halo_bispectrum ---
+   The three-point check of a catalogue, by the FFT estimator of Scoccimarro (2000) / Sefusatti et al. (2016): per k-bin the halo
+   contrast is band-filtered, and the sum over cells of the product of three filtered fields is the sum of delta delta delta over
+   the closed triangles of the three bins.  The list, the mass bins, the deposit, the contrast, the forward transform and the
+   collective protocol are pf_halo_correlation's, word for word: flags, inclusive mass ranges, pos + vel * vfac on axis los (vel ==
+   NULL: real space), the single wrap, integer CIC / NGP, the headroom refusal, an empty mass bin launching nothing and returning
+   zeros, every rank passing the whole list, the agreeing all-reduce (which also covers kmin, dk and nk), "context left as found".
+   k-bins: nk linear bins in integer units of the fundamental, kmin >= 1, dk >= 1, 1 <= nk <= PF_BISPEC_MAX_KBINS.  Bin i takes the
+     modes with (kmin + i dk)^2 <= k2 < (kmin + (i + 1) dk)^2, k2 the exact integer of pf_power_spectrum; kmax = kmin + nk dk.  A
+     sum over cells closes triangles modulo n; with 3 kmax <= n every component sum is below n in magnitude and only true triangles
+     close, so 3 kmax > n is refused: a condition, not a tolerance.
+   Mask pass, on the ky-slab half-spectrum: the data field of bin i holds a stored mode inside the bin as it is -- with
+     PF_HALO_DECONVOLVE each part times the window factor (c[|kx|] c[|ky|]) c[kz] of pf_halo_correlation's table, once -- rounded
+     to the field type F, and zero outside (k = 0 is in no bin); the count field holds ((F)N3, 0) inside and zero outside.  A mode
+     inside the bin that is not finite is written as zero and counted with its Hermitian weight in nonfinite_modes; the same pass
+     counts the bin's modes with their Hermitian weights, kmodes[i].  The count fields are made once per call and read no spectrum.
+   Reverse transform: the context's, with its 1 / N3: D_i(x), the band-filtered contrast, and I_i(x) with I_i(0) == kmodes[i].
+   Keep pass: every reversed field is copied into a compact store [nxl][n][n] of F, nk stores allocated for the call; the pass
+     finds the largest |value| M_i (over the ranks through per-rank slots of the all-reduce) and the cells that are not finite,
+     which are stored as zero and counted in nonfinite_cells.
+   Triangles: the ordered bin triples i <= j <= l with kmin + l dk < 2 kmin + (i + j + 2) dk; the others cannot close and are
+     neither computed nor returned.  pf_bispectrum_triangles returns their number nt (-1: kmin, dk or nk out of range) and, with
+     ijl != NULL, the list [nt][3] in lexicographic order; the outputs below are indexed by it.
+   Triple pass: per closed triple and cell t = (a b) c in double of the three stores' values, each product rounded once; |t| enters
+     the positive or the negative sum of the triple in pf_power_spectrum's fixed point under the exponent of M = (M_i M_j) M_l,
+     formed the same way (rounding is monotone: |t| <= M; no scan pass).  Integer adds only, no floating-point atomics: the bits
+     are the same for any launch geometry, any order of the list and any number of ranks.  psum[i] = sum_x D_i^2 likewise, one
+     positive sum under M_i M_i.  The count fields go through the same pass.
+   Outputs: bsum[b nt + t] = positive - negative of the data fields of mass bin b: the sum over the closed triangles of delta delta
+     delta / N3^2.  ntri[t] = positive - negative of the count fields over N3: the number of (k1 in i, k2 in j, k3 in l) with k1 +
+     k2 + k3 = 0, an integer up to the transforms' error, returned once.  psum[b nk + i]; kmodes[i].  B = Box^6 bsum / (N3 ntri) and
+     P_i = Box^3 psum / (N3 kmodes) are the caller's to form, as is the shot noise (unit weights: from info[b].halo.selected).
+     info[b].halo as pf_halo_correlation fills it (nonfinite_modes: summed over the k-bins), cells = N3, nonfinite_cells summed
+     over the k-bins and the ranks.
+   Refused (1, pf_last_error names pf_halo_bispectrum, nothing launched): everything pf_halo_correlation refuses of the list; a null
+     kmodes, ntri, bsum, psum or info; kmin, dk or nk out of range; 3 kmax > n; n > 1024 (a limb counter takes N3 terms below 2^32
+     and stays below 2^63 up to there); a failed allocation, naming its bytes (the nk stores, one copy of the spectrum, the tables)
+     and, on several ranks, agreed on before any collective.
+   pf_debug_bispec_mask: test tap without a context: the production mask pass of k-bin `bin` on the rows y0 .. y0 + nyl - 1 of the
+     caller's fp64 ky-slab [nyl][n][n/2+1] complex; kind 0 the data field, 1 the count field (here the spectrum is read and a mode
+     that is not finite is zeroed and counted in either kind); flags: PF_HALO_NGP | PF_HALO_DECONVOLVE -> the field widened to fp64,
+     kmodes and nonfinite_modes of the rows.
+   pf_debug_bispec_triples: test tap without a context: the production keep, triple and pair passes on the planes x0 .. x0 + nxl - 1
+     of the caller's nk fp64 real fields [nk][nxl][n][n], converted to field_bytes on the way in -> sums[nt], parts[2][nt] (the
+     positive sums: of the positive terms, of the negated negative ones), pair[nk], maxima[nk], nonfinite_cells.
+   pf_debug_bispec_times: with PF_BISPEC_TIMES=1 in the environment, ms[0..6] = device ms of the selection, the deposits, the
+     contrasts, the transforms (forward and reverse), the mask, keep and triple passes of the calling thread's last
+     pf_halo_bispectrum, summed over its mass bins and the count fields; 0 otherwise. */
+#define PF_BISPEC_MAX_KBINS 32
+typedef struct { pf_halo_info halo; unsigned long long cells, nonfinite_cells; } pf_bispec_info;
+int pf_bispectrum_triangles(int kmin, int dk, int nk, int *ijl);
+int pf_halo_bispectrum(pf_ctx *ctx, int flags, size_t count, const double *pos, const double *vel,
+                       double scale, double vfac, int los, const int *mass, int nbins, const int *mass_range,
+                       int kmin, int dk, int nk,
+                       unsigned long long *kmodes, double *ntri, double *bsum, double *psum, pf_bispec_info *info);
+int pf_debug_bispec_mask(int field_bytes, int n, int y0, int nyl, const double *spec, int flags, int kind,
+                         int kmin, int dk, int nk, int bin, double *spec_out,
+                         unsigned long long *kmodes, unsigned long long *nonfinite_modes);
+int pf_debug_bispec_triples(int field_bytes, int n, int x0, int nxl, const double *fields, int kmin, int dk, int nk,
+                            double *sums, double *parts, double *pair, double *maxima, unsigned long long *nonfinite_cells);
+int pf_debug_bispec_times(double *ms);   /* PF_BISPEC_TIMES=1: select, deposit, contrast, transforms, mask, keep, triples */
+
 /* --- measurement --- */
 int pf_get_cputime(pf_ctx *ctx, pf_cputime *t);
 int pf_reset_cputime(pf_ctx *ctx);

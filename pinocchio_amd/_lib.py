@@ -158,6 +158,13 @@ class CorrInfo(C.Structure):
     _fields_ = [("halo", HaloInfo), ("cells", C.c_ulonglong), ("nonfinite_cells", C.c_ulonglong)]
 
 
+BISPEC_MAX_KBINS = 32   # PF_BISPEC_MAX_KBINS
+
+
+class BispecInfo(C.Structure):
+    _fields_ = [("halo", HaloInfo), ("cells", C.c_ulonglong), ("nonfinite_cells", C.c_ulonglong)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -355,6 +362,13 @@ PROTOTYPES = {
                                        C.POINTER(C.c_ulonglong)]),
     "pf_debug_corr_passes": (C.c_int, [C.POINTER(C.c_int)]),
     "pf_debug_corr_times": (C.c_int, [_dp]),
+    "pf_bispectrum_triangles": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "pf_halo_bispectrum": (C.c_int, [_vp, C.c_int, C.c_size_t, _dp, _dp, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
+                                     C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong), _dp, _dp, _dp, C.POINTER(BispecInfo)]),
+    "pf_debug_bispec_mask": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp,
+                                       C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "pf_debug_bispec_triples": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_ulonglong)]),
+    "pf_debug_bispec_times": (C.c_int, [_dp]),
     "pf_get_cputime": (C.c_int, [_vp, C.POINTER(CpuTime)]),
     "pf_reset_cputime": (C.c_int, [_vp]),
     "pf_kernel_stats": (C.c_int, [_vp, C.POINTER(KernelStat), C.c_int, C.POINTER(C.c_int)]),

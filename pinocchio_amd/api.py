@@ -373,6 +373,64 @@ def debug_corr_shells(real, x0: int = 0, field_bytes: int = 8, los: int = 2):
     return {"ncells": nc, "r2sum": r2, "xi": xi, "parts": parts, "nonfinite_cells": int(bad.value)}
 
 
+BISPEC_MAX_KBINS = _lib.BISPEC_MAX_KBINS
+BISPEC_TIME_KEYS = ("select", "deposit", "contrast", "transform", "mask", "keep", "triples")
+
+
+def bispectrum_triangles(kmin: int, dk: int, nk: int):
+    """the ordered triples i <= j <= l of the nk linear k-bins [kmin + i dk, kmin + (i + 1) dk) that can close a triangle, in
+    lexicographic order, as an int32 array [nt][3]: what the outputs of halo_bispectrum are indexed by (pf_bispectrum_triangles)"""
+    L = _lib.load()
+    nt = L.pf_bispectrum_triangles(int(kmin), int(dk), int(nk), None)
+    if nt < 0:
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_bispectrum_triangles failed")
+    ijl = np.zeros((nt, 3), dtype=np.int32)
+    L.pf_bispectrum_triangles(int(kmin), int(dk), int(nk), ijl.ctypes.data_as(C.POINTER(C.c_int)))
+    return ijl
+
+
+def debug_bispec_times():
+    """device ms of the phases of the last halo_bispectrum, summed over its mass bins and the count fields: (select, deposit,
+    contrast, transforms, mask, keep, triples); zeros without PF_BISPEC_TIMES=1 (pf_debug_bispec_times)"""
+    ms = (C.c_double * 7)()
+    _lib.load().pf_debug_bispec_times(ms)
+    return tuple(float(x) for x in ms)
+
+
+def debug_bispec_mask(spec, kmin: int, dk: int, nk: int, bin: int, y0: int = 0, field_bytes: int = 8, ngp: bool = False, deconvolve: bool = False, kind: int = 0):
+    """the production mask pass of halo_bispectrum for k-bin `bin` on the rows y0 .. y0 + nyl - 1 of a ky-slab [nyl][n (kx)][n/2+1]
+    complex128 (pf_debug_bispec_mask): kind 0 the data field, 1 the count field -> (the field as complex128, {kmodes,
+    nonfinite_modes})"""
+    L = _lib.load()
+    spec = np.ascontiguousarray(spec, dtype=np.complex128)
+    if spec.ndim != 3 or spec.shape[2] != spec.shape[1] // 2 + 1:
+        raise ValueError(f"a ky-slab [nyl][n][n/2+1], not {spec.shape}")
+    nyl, n = spec.shape[:2]
+    out = np.zeros(spec.shape, dtype=np.complex128)
+    km, bad = C.c_ulonglong(0), C.c_ulonglong(0)
+    if L.pf_debug_bispec_mask(int(field_bytes), n, int(y0), nyl, _dp(spec.view(np.float64)), _matter_flags(ngp, deconvolve), int(kind), int(kmin), int(dk), int(nk), int(bin),
+                              _dp(out.view(np.float64)), C.byref(km), C.byref(bad)):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_bispec_mask failed")
+    return out, {"kmodes": int(km.value), "nonfinite_modes": int(bad.value)}
+
+
+def debug_bispec_triples(fields, kmin: int, dk: int, nk: int, x0: int = 0, field_bytes: int = 8):
+    """the production keep, triple and pair passes of halo_bispectrum on the planes x0 .. x0 + nxl - 1 of nk real fields
+    [nk][nxl][n][n] float64 (pf_debug_bispec_triples) -> sums[nt] (positive - negative), parts[2][nt] (the positive sums), pair[nk],
+    maxima[nk] and nonfinite_cells"""
+    L = _lib.load()
+    fields = np.ascontiguousarray(fields, dtype=np.float64)
+    if fields.ndim != 4 or fields.shape[0] != nk or fields.shape[2] != fields.shape[3]:
+        raise ValueError(f"fields [nk][nxl][n][n] with nk = {nk}, not {fields.shape}")
+    nxl, n = fields.shape[1:3]
+    nt = len(bispectrum_triangles(kmin, dk, nk))
+    sums, parts, pair, maxima = np.zeros(nt), np.zeros((2, nt)), np.zeros(nk), np.zeros(nk)
+    bad = C.c_ulonglong(0)
+    if L.pf_debug_bispec_triples(int(field_bytes), n, int(x0), nxl, _dp(fields), int(kmin), int(dk), int(nk), _dp(sums), _dp(parts), _dp(pair), _dp(maxima), C.byref(bad)):
+        raise PinfmaxError(L.pf_last_error().decode() or "pf_debug_bispec_triples failed")
+    return {"sums": sums, "parts": parts, "pair": pair, "maxima": maxima, "nonfinite_cells": int(bad.value)}
+
+
 _ARITH ={"fast": _lib.ARITH_FAST, "exact": _lib.ARITH_EXACT}
 # pf_census_cell: an outlier of the flavour census
 CENSUS_CELL_DTYPE = np.dtype([("cell", "<u8"), ("fast", "<f8"), ("exact", "<f8"), ("rmax_fast", "<i4"), ("rmax_exact", "<i4")], align=False)
@@ -1762,6 +1820,45 @@ class Fmax:
         out["variance"] = xi[:, 0, 0].copy()
         if box is not None:
             out["r"] = (float(box) / self.n) * np.sqrt(r2.astype(np.float64) / f)
+        return out
+
+    def halo_bispectrum(self, pos, vel, mass, ranges, kmin: int, dk: int, nk: int, scale: float = 1.0, vfac: float = 0.0, los: int = 2, mass_weight: bool = False,
+                        ngp: bool = False, deconvolve: bool = False, box=None) -> dict:
+        """the bispectrum of the haloes per mass bin by the FFT estimator, in nk linear k-bins [kmin + i dk, kmin + (i + 1) dk) in units
+        of the fundamental (pf_halo_bispectrum; collective like halo_correlation, whose list, mass bins and flags these are; 3 (kmin + nk
+        dk) <= n): triangles[nt][3] (bispectrum_triangles), kmodes[nk], ntri[nt], bsum[b][nt], psum[b][nk] and the counters of
+        pf_bispec_info as arrays over the mass bins.  Formed here for convenience with the box length `box`: k[nk] the bin centres, pk[b][nk]
+        = box^3 psum / (N3 kmodes), B[b][nt] = box^6 bsum / (N3 ntri) and the reduced Q[b][nt] = B / (P_i P_j + P_j P_l + P_l P_i); no
+        shot noise is taken off"""
+        pos, mass = _halo_list(pos, mass)
+        vel = _halo_vel(vel, pos)
+        rg = np.ascontiguousarray(ranges, dtype=np.int32)
+        if rg.ndim != 2 or rg.shape[1] != 2:
+            raise ValueError(f"ranges [nbins][2], not {rg.shape}")
+        nbins = rg.shape[0]
+        tri = bispectrum_triangles(kmin, dk, nk)
+        nt = len(tri)
+        km, ntri = np.zeros(nk, dtype=np.uint64), np.zeros(nt)
+        bsum, psum = np.zeros((max(nbins, 1), nt)), np.zeros((max(nbins, 1), nk))
+        info = (_lib.BispecInfo * max(nbins, 1))()
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        self._chk(self.L.pf_halo_bispectrum(self.h, _halo_flags(ngp, deconvolve, mass_weight), len(mass), _dp(pos), None if vel is None else _dp(vel), float(scale), float(vfac),
+                                            int(los), ip(mass), nbins, ip(rg), int(kmin), int(dk), int(nk), km.ctypes.data_as(C.POINTER(C.c_ulonglong)), _dp(ntri), _dp(bsum),
+                                            _dp(psum), info))
+        per = [_halo_info(info[b].halo) for b in range(nbins)]
+        out = {"triangles": tri, "kmodes": km, "ntri": ntri, "bsum": bsum, "psum": psum}
+        for k in per[0]:
+            out[k] = [p[k] for p in per] if k == "weight2" else np.array([p[k] for p in per], dtype=np.uint64)
+        out["cells"] = np.array([int(info[b].cells) for b in range(nbins)], dtype=np.uint64)
+        out["nonfinite_cells"] = np.array([int(info[b].nonfinite_cells) for b in range(nbins)], dtype=np.uint64)
+        if box is not None:
+            N3, L = float(self.n) ** 3, float(box)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                out["k"] = (2.0 * np.pi / L) * (kmin + dk * (np.arange(nk) + 0.5))
+                pk = L ** 3 * psum / (N3 * km.astype(np.float64))
+                out["pk"], out["B"] = pk, L ** 6 * bsum / (N3 * ntri)
+                pi, pj, pl = pk[:, tri[:, 0]], pk[:, tri[:, 1]], pk[:, tri[:, 2]]
+                out["Q"] = out["B"] / (pi * pj + pj * pl + pl * pi)
         return out
 
     # -- measurement ------------------------------------------------------

@@ -7,7 +7,10 @@
 // velocities (pf_halo_pos_rsd) and the multipole shell pass (pf_multipole_shells_device) in place of the plain one.
 // pf_halo_correlation is the same body again up to the forward transform; behind it the form passes (pf_corr_form_device: delta_h(k)
 // -> |delta_h|^2 / N^3 and Re(delta_h delta*) / N^3), the context's reverse transform (pf_ctx_matter_reverse) and the shell pass in
-// separation space (pf_corr_shells_device), all three pf_power.hip's.
+// separation space (pf_corr_shells_device), all three pf_power.hip's.  pf_halo_bispectrum is the same body once more up to the forward
+// transform; behind it delta_h(k) is copied into a field of its own and handed to pf_bispec_device (pf_bispec.hip: per k-bin the mask
+// pass, the context's reverse transform and the keep pass, then the triple pass), after the count fields of the call have gone the
+// same way once.
 //
 //  k_halo_select    one halo per lane, every bin in one read of the list: the class of its position (ballots) and, per bin, the
 //                   counts and the integer sums of W and of the high and low halves of W^2, reduced over the wave by shuffles; one
@@ -165,8 +168,10 @@ __global__ void __launch_bounds__(PF_HALO_BLOCK) k_halo_contrast(const u64 *grid
 // the reverse transforms with the forward ones
 enum { HT_SELECT = 0, HT_DEPOSIT, HT_CONTRAST, HT_TRANSFORM, HT_SHELLS, HT_COUNT };
 enum { CT_FORM = HT_SHELLS, CT_SHELLS, CT_COUNT };   // the phases of the correlation call: the first four as above
+enum { BT_MASK = HT_SHELLS, BT_KEEP, BT_TRIPLES, BT_COUNT };   // ... and of the bispectrum call (PF_BISPEC_TIMES=1)
 static thread_local double halo_last_ms[HT_COUNT] = {0.0, 0.0, 0.0, 0.0, 0.0};
 static thread_local double corr_last_ms[CT_COUNT] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+static thread_local double bispec_last_ms[BT_COUNT] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 extern "C" int pf_debug_halo_times(double *ms) {
   if (!ms) return 1;
   for (int i = 0; i < HT_COUNT; i++) ms[i] = halo_last_ms[i];
@@ -177,12 +182,18 @@ extern "C" int pf_debug_corr_times(double *ms) {
   for (int i = 0; i < CT_COUNT; i++) ms[i] = corr_last_ms[i];
   return 0;
 }
+extern "C" int pf_debug_bispec_times(double *ms) {
+  if (!ms) return 1;
+  for (int i = 0; i < BT_COUNT; i++) ms[i] = bispec_last_ms[i];
+  return 0;
+}
 struct HaloTimer {
   std::vector<hipEvent_t> ev; std::vector<int> phase; hipStream_t st; bool on; double *dst;
-  HaloTimer(hipStream_t st_, bool corr) : st(st_), dst(corr ? corr_last_ms : halo_last_ms) {
-    const char *env = getenv(corr ? "PF_CORR_TIMES" : "PF_HALO_TIMES");
+  // kind: 0 the power and multipole calls, 1 the correlation call, 2 the bispectrum call
+  HaloTimer(hipStream_t st_, int kind) : st(st_), dst(kind == 2 ? bispec_last_ms : kind == 1 ? corr_last_ms : halo_last_ms) {
+    const char *env = getenv(kind == 2 ? "PF_BISPEC_TIMES" : kind == 1 ? "PF_CORR_TIMES" : "PF_HALO_TIMES");
     on = env && atoi(env) != 0;
-    for (int i = 0; i < (corr ? (int)CT_COUNT : (int)HT_COUNT); i++) dst[i] = 0.0;
+    for (int i = 0; i < (kind == 2 ? (int)BT_COUNT : kind == 1 ? (int)CT_COUNT : (int)HT_COUNT); i++) dst[i] = 0.0;
   }
   // what ran since the last mark belongs to `ph` (-1: to none)
   void mark(int ph) {
@@ -205,10 +216,14 @@ struct HaloTimer {
 
 // what a call holds on the device: the list, the selection counters, the grid of the slab and the words (counters and shell tables
 // of every bin, then what the ranks agree on)
-struct HaloBufs { double *pos, *vlos; int *mass; u64 *sel, *grid, *words; void *extra; };   // extra: the cross spectrum of pf_halo_correlation
+// extra: the cross spectrum of pf_halo_correlation, the copy of delta_h(k) of pf_halo_bispectrum; stores: the kept fields of the latter
+struct HaloBufs { double *pos, *vlos; int *mass; u64 *sel, *grid, *words; void *extra, *stores; };
 struct HaloGuard {
   HaloBufs *b;
-  ~HaloGuard() { hipFree(b->pos); hipFree(b->vlos); hipFree(b->mass); hipFree(b->sel); hipFree(b->grid); hipFree(b->words); hipFree(b->extra); memset(b, 0, sizeof(*b)); }
+  ~HaloGuard() {
+    hipFree(b->pos); hipFree(b->vlos); hipFree(b->mass); hipFree(b->sel); hipFree(b->grid); hipFree(b->words); hipFree(b->extra); hipFree(b->stores);
+    memset(b, 0, sizeof(*b));
+  }
 };
 
 static bool halo_finite(double x) { return x - x == 0.0; }
@@ -327,12 +342,21 @@ static int halo_refuse(const char *who, pf_ctx *c, const PfSpecView &sv) {
 // the body of pf_halo_power (HM_POWER: vel null, vfac 0; power and cross [nbins][nb]), of pf_halo_multipoles (HM_MULTI: the list
 // moved along axis los, the multipole shell pass, power and cross [nbins][3][nb]) and of pf_halo_correlation (HM_CORR: the list moved
 // likewise; behind the forward transform the form passes, the reverse transforms and the shell pass in separation space; nmodes and
-// k2sum are ncells and r2sum, power and cross xi and xi_cross [nbins][3][nb]; nonfinite_cells [nbins], null otherwise)
-enum { HM_POWER = 0, HM_MULTI, HM_CORR };
+// k2sum are ncells and r2sum, power and cross xi and xi_cross [nbins][3][nb]; nonfinite_cells [nbins], null otherwise) and of
+// pf_halo_bispectrum (HM_BISPEC: the list moved likewise; behind the forward transform pf_bispec_device on a copy of delta_h(k); bq:
+// the k-bins and the outputs of that call; nmodes, k2sum and power are its kmodes, ntri and bsum, so that a null one is refused where
+// every null is; cross null: no density is needed)
+enum { HM_POWER = 0, HM_MULTI, HM_CORR, HM_BISPEC };
+struct HaloBispec { int kmin, dk, nk; u64 *kmodes; double *ntri, *bsum, *psum; };
+static void halo_bispec_mark(void *timer, int ph) {
+  static const int of[4] = {HT_TRANSFORM, BT_MASK, BT_KEEP, BT_TRIPLES};   // PF_BISPEC_PH_* -> the phases of the timer
+  ((HaloTimer *)timer)->mark(ph < 0 ? -1 : of[ph]);
+}
 static int halo_spectra(const char *who, int mode, pf_ctx *c, int flags, size_t count, const double *pos, const double *vel, double scale, double vfac, int los, const int *mass,
-                        int nbins, const int *mass_range, unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross, pf_halo_info *info, u64 *nonfinite_cells = nullptr) {
+                        int nbins, const int *mass_range, unsigned long long *nmodes, unsigned long long *k2sum, double *power, double *cross, pf_halo_info *info, u64 *nonfinite_cells = nullptr,
+                        const HaloBispec *bq = nullptr) {
   if (!c) return pf_fail(0, "%s: null argument", who);
-  const bool multi = mode != HM_POWER, corr = mode == HM_CORR;
+  const bool multi = mode != HM_POWER, corr = mode == HM_CORR, bis = mode == HM_BISPEC;
   PfSpecView sv;
   pf_ctx_spec_geometry(c, &sv);
   if (sv.P > 1 && !pf_ctx_exchange_installed(c))
@@ -347,26 +371,31 @@ static int halo_spectra(const char *who, int mode, pf_ctx *c, int flags, size_t 
   int bad = 0;
   if (!nmodes || !k2sum || !power) bad = pf_fail(task, "%s: null argument", who);
   if (!bad) bad = halo_check_list(who, task, flags, count, pos, scale, mass, nbins, mass_range, info);
+  if (!bad && bis && !bq->psum) bad = pf_fail(task, "%s: null argument", who);
   if (!bad && multi) bad = halo_check_rsd(who, task, vel, vfac, los);
   if (!bad && cross) bad = pf_ctx_spec_view(c, who, 0, &sv);   // "density not set" (which = 0: nothing is launched)
+  if (!bad && bis) bad = pf_bispec_check_bins(who, task, bq->kmin, bq->dk, bq->nk, n);
+  if (!bad && bis && n > 1024) bad = pf_fail(task, "%s: a grid of %d is above 1024: a limb counter takes n^3 terms below 2^32 and would pass 2^63", who, n);
   HaloBufs b;
   memset(&b, 0, sizeof(b));
   HaloGuard guard{&b};
   // (the correlation call: the tables of the auto field, then those of the cross field, each of corr_words)
   const size_t nb = (size_t)pf_power_nbins(n), corr_words = pf_corr_shells_words(n, P);
-  const size_t shell_words = corr ? 2 * corr_words : multi ? pf_multipole_shells_words(n, P) : pf_matter_shells_words(n, P), bin_words = MC_WORDS + shell_words;
+  const size_t shell_words = bis ? 0 : corr ? 2 * corr_words : multi ? pf_multipole_shells_words(n, P) : pf_matter_shells_words(n, P), bin_words = MC_WORDS + shell_words;
   const size_t orders = multi ? PF_MULTIPOLE_ORDERS : 1;
   const size_t fetch_words = (size_t)PF_HALO_MAX_BINS * (2 + (size_t)P);
   const size_t agree_words = halo_agree_words(P) > fetch_words ? halo_agree_words(P) : fetch_words;
-  const size_t deconv_words = corr ? (size_t)(n / 2 + 1) : 0;                      // the deconvolution table of the form passes, behind everything
-  const size_t words = bad ? 0 : (size_t)(nbins + 1) * bin_words + agree_words + deconv_words;   // (the bin behind the last: the tables of a call whose bins are all empty)
+  const size_t deconv_words = corr || bis ? (size_t)(n / 2 + 1) : 0;               // the deconvolution table of the form passes, behind everything
+  const size_t bispec_words = bis && !bad ? pf_bispec_words(bq->kmin, bq->dk, bq->nk, P) : 0;   // ... and behind it the tables of pf_bispec_device
+  const size_t words = bad ? 0 : (size_t)(nbins + 1) * bin_words + agree_words + deconv_words + bispec_words;   // (the bin behind the last: the tables of a call whose bins are all empty)
   size_t field_bytes = 0;
-  void *rev = corr ? pf_ctx_matter_reverse_field(c, &field_bytes) : nullptr;       // where the reverse transform works
-  const size_t extra_bytes = corr && cross ? field_bytes : 0;
-  const size_t list = count ? count : 1, bytes = list * (vel ? 36 : 28) + HS_WORDS * 8 + cv.ncell * 8 + words * 8 + extra_bytes;
+  void *rev = corr || bis ? pf_ctx_matter_reverse_field(c, &field_bytes) : nullptr;   // where the reverse transform works
+  const size_t extra_bytes = (corr && cross) || bis ? field_bytes : 0;
+  const size_t store_bytes = bis && !bad ? (size_t)bq->nk * cv.ncell * sv.fb : 0;      // the nk kept fields
+  const size_t list = count ? count : 1, bytes = list * (vel ? 36 : 28) + HS_WORDS * 8 + cv.ncell * 8 + words * 8 + extra_bytes + store_bytes;
   if (!bad && (hipMalloc((void **)&b.pos, list * 24) != hipSuccess || (vel && hipMalloc((void **)&b.vlos, list * 8) != hipSuccess) || hipMalloc((void **)&b.mass, list * 4) != hipSuccess ||
                hipMalloc((void **)&b.sel, HS_WORDS * 8) != hipSuccess || hipMalloc((void **)&b.grid, cv.ncell * 8) != hipSuccess || hipMalloc((void **)&b.words, words * 8) != hipSuccess ||
-               (extra_bytes && hipMalloc(&b.extra, extra_bytes) != hipSuccess))) {
+               (extra_bytes && hipMalloc(&b.extra, extra_bytes) != hipSuccess) || (store_bytes && hipMalloc(&b.stores, store_bytes) != hipSuccess))) {
     (void)hipGetLastError();
     bad = pf_fail(task, "%s: cannot allocate %zu bytes of scratch on the device", who, bytes);
   }
@@ -381,7 +410,7 @@ static int halo_spectra(const char *who, int mode, pf_ctx *c, int flags, size_t 
   bins.nbins = nbins;
   for (int k = 0; k < nbins; k++) { bins.lo[k] = mass_range[2 * k]; bins.hi[k] = mass_range[2 * k + 1]; }
   HLHIP(task, who, hipMemsetAsync(b.words, 0, (size_t)(nbins + 1) * bin_words * 8, st));
-  HaloTimer timer(st, corr);
+  HaloTimer timer(st, bis ? 2 : corr ? 1 : 0);
   std::vector<pf_halo_info> hi(nbins);
   const int full = halo_select(who, task, h, bins, b.sel, hi.data(), &timer, st);
   if (P > 1) {   // the same list on every rank, and no rank that refuses
@@ -390,6 +419,7 @@ static int halo_spectra(const char *who, int mode, pf_ctx *c, int flags, size_t 
     if (full) a[a.size() - 1] = 1;
     else {
       mine[0] = (u64)count; mine[1] = ((u64)nbins << 8) | (u64)flags;
+      if (bis) mine[1] |= ((u64)bq->nk << 16) | ((u64)bq->dk << 24) | ((u64)bq->kmin << 44);   // (dk and kmin are below 2^20: 3 kmax <= n)
       for (int k = 0; k < nbins; k++) { mine[2 + k] = hi[k].selected; mine[2 + PF_HALO_MAX_BINS + k] = hi[k].weight_sum; }
       mine[2 + 2 * PF_HALO_MAX_BINS] = ((u64)(vel != nullptr) << 8) | (u64)los;
       memcpy(&mine[3 + 2 * PF_HALO_MAX_BINS], &vfac, 8);
@@ -400,18 +430,31 @@ static int halo_spectra(const char *who, int mode, pf_ctx *c, int flags, size_t 
     if (a[a.size() - 1]) return pf_fail(task, "%s: refused on another rank of the context", who);
     for (int p = 0; p < P; p++)
       if (memcmp(a.data() + (size_t)p * HA_SLOT, own.data(), HA_SLOT * 8))
-        return pf_fail(task, "%s: rank %d holds another list, other bins, other flags or another line of sight than rank %d (%llu haloes there, %zu here)", who, p, sv.rank,
-                       a[(size_t)p * HA_SLOT], count);
+        return pf_fail(task, "%s: rank %d holds another list, other bins, other flags%s or another line of sight than rank %d (%llu haloes there, %zu here)", who, p,
+                       bis ? ", other k-bins" : "", sv.rank, a[(size_t)p * HA_SLOT], count);
   } else if (full) return 1;
   // per bin: deposit, contrast, transform, shell sums; the tables stay on the device until every bin is through
   const u64 n3 = (u64)n * (u64)n * (u64)n;
   pf_ctx *coll = P > 1 ? c : nullptr;
   std::vector<PfShellSums> g(nbins + 1), gx(nbins + 1);   // gx: the cross field of the correlation call
   const double *Ctab = nullptr;
-  if (corr) {
+  if (corr || bis) {
     if (pf_corr_deconv_upload(who, task, flags & (PF_HALO_NGP | PF_HALO_DECONVOLVE), n, (double *)(agree + agree_words), &Ctab, st)) return 1;
     if (b.extra) HLHIP(task, who, hipMemsetAsync(b.extra, 0, extra_bytes, st));   // (the padding of its rows: the form pass writes the modes alone)
     timer.mark(-1);
+  }
+  // the bispectrum call: the geometry and the tables of pf_bispec_device; the count fields once, whatever the mass bins hold
+  const PfBispecGeom bg = {n, sv.fb, sv.y0, sv.nyl, mc.x0, cv.nxl, sv.rank, P, sv.nzp, mc.rpitch};
+  const PfBispecBins kb = {bis ? bq->kmin : 0, bis ? bq->dk : 0, bis ? bq->nk : 0};
+  u64 *bwords = agree + agree_words + deconv_words;
+  const int nt = bis ? pf_bispectrum_triangles(kb.kmin, kb.dk, kb.nk, nullptr) : 0;
+  std::vector<double> bsum((size_t)nbins * nt, 0.0), psum((size_t)nbins * kb.nk, 0.0), ntri(nt, 0.0);
+  std::vector<u64> kmodes(kb.nk, 0), bad_modes(nbins, 0), bad_cells(nbins, 0);
+  if (bis) {
+    PfBispecOut bo = {ntri.data(), nullptr, nullptr, nullptr, kmodes.data(), 0, 0};
+    if (pf_bispec_device(who, task, c, bg, kb, nullptr, 1, nullptr, rev, b.stores, bwords, halo_bispec_mark, &timer, &bo, st)) return 1;
+    const double dn3 = (double)n * (double)n * (double)n;
+    for (int t = 0; t < nt; t++) ntri[t] = ntri[t] / dn3;
   }
   int first = -1;
   for (int k = 0; k < nbins; k++) {
@@ -424,6 +467,17 @@ static int halo_spectra(const char *who, int mode, pf_ctx *c, int flags, size_t 
     if (pf_ctx_matter_forward(c)) return 1;
     timer.mark(HT_TRANSFORM);
     const int sflags = flags & (PF_HALO_NGP | PF_HALO_DECONVOLVE);
+    if (bis) {
+      // delta_h(k) into the field of its own: the reverse transform overwrites the scratch spectrum with more than one rank, and with
+      // one rank it works where the spectrum stands
+      HLHIP(task, who, hipMemcpyAsync(b.extra, mc.field, (size_t)n * sv.nyl * sv.nzp * 2 * sv.fb, hipMemcpyDeviceToDevice, st));
+      timer.mark(BT_MASK);
+      PfBispecOut bo = {bsum.data() + (size_t)k * nt, nullptr, psum.data() + (size_t)k * kb.nk, nullptr, nullptr, 0, 0};
+      if (pf_bispec_device(who, task, c, bg, kb, b.extra, 0, Ctab, rev, b.stores, bwords, halo_bispec_mark, &timer, &bo, st)) return 1;
+      bad_modes[k] = bo.nonfinite_modes; bad_cells[k] = bo.nonfinite_cells;
+      if (first < 0) first = k;
+      continue;
+    }
     if (corr) {
       // the cross spectrum first, into the field of its own; then the auto spectrum where the reverse transform works (with one
       // rank that is where delta_h(k) stands: in place).  The reverse transform overwrites mc.field with more than one rank: by
@@ -452,7 +506,7 @@ static int halo_spectra(const char *who, int mode, pf_ctx *c, int flags, size_t 
     timer.mark(HT_SHELLS);
     if (first < 0) first = k;
   }
-  if (first < 0) {   // every bin is empty: nmodes and k2sum, which depend on the grid alone, from the shell pass over a spectrum of zeros
+  if (first < 0 && !bis) {   // every bin is empty: nmodes and k2sum, which depend on the grid alone, from the shell pass over a spectrum of zeros
     first = nbins;
     u64 *counters = b.words + (size_t)nbins * bin_words;
     if (corr) {   // (ncells and r2sum from the separation-space pass over a field of zeros)
@@ -469,18 +523,27 @@ static int halo_spectra(const char *who, int mode, pf_ctx *c, int flags, size_t 
   std::vector<u64> hu(2 * nb), slots(MC_WORDS);
   const size_t per = orders * nb;                       // doubles of a bin in power and in cross; out holds power, then cross
   std::vector<double> hd(2 * per);
-  HLHIP(task, who, hipMemcpyAsync(hu.data(), g[first].nm, hu.size() * 8, hipMemcpyDeviceToHost, st));
-  HLHIP(task, who, hipStreamSynchronize(st));
+  if (!bis) {
+    HLHIP(task, who, hipMemcpyAsync(hu.data(), g[first].nm, hu.size() * 8, hipMemcpyDeviceToHost, st));
+    HLHIP(task, who, hipStreamSynchronize(st));
+  }
   std::vector<u64> grid_words((size_t)nbins * (2 + (size_t)P), 0);   // per bin: empty cells, modes that are not finite, the largest cell of every rank
   for (int k = 0; k < nbins; k++) {
     hi[k].modes = n3;
     if (!hi[k].weight_sum) {
       hi[k].empty_cells = n3;
-      if (corr) nonfinite_cells[k] = 0;
-      for (size_t s = 0; s < per; s++) { power[(size_t)k * per + s] = 0.0; if (cross) cross[(size_t)k * per + s] = 0.0; }
+      if (corr || bis) nonfinite_cells[k] = 0;
+      for (size_t s = 0; s < (bis ? 0 : per); s++) { power[(size_t)k * per + s] = 0.0; if (cross) cross[(size_t)k * per + s] = 0.0; }
       continue;
     }
     HLHIP(task, who, hipMemcpyAsync(slots.data(), b.words + (size_t)k * bin_words, MC_WORDS * 8, hipMemcpyDeviceToHost, st));
+    if (bis) {   // the sums are on the host already, summed over the ranks; the counters of the contrast pass alone are fetched
+      HLHIP(task, who, hipStreamSynchronize(st));
+      nonfinite_cells[k] = bad_cells[k];
+      u64 *w = grid_words.data() + (size_t)k * (2 + (size_t)P), unused;
+      halo_reduce_slots(slots.data(), &w[0], &w[2 + sv.rank], &unused);
+      continue;
+    }
     u64 bad_cells[2] = {0, 0};
     if (corr) {   // xi of each field [3][nb] from the tables of its own; the cells that are not finite stand behind the limbs, summed over the ranks already
       HLHIP(task, who, hipMemcpyAsync(hd.data(), g[k].out, per * 8, hipMemcpyDeviceToHost, st));
@@ -501,10 +564,13 @@ static int halo_spectra(const char *who, int mode, pf_ctx *c, int flags, size_t 
   for (int k = 0; k < nbins; k++) {
     if (!hi[k].weight_sum) continue;
     const u64 *w = grid_words.data() + (size_t)k * (2 + (size_t)P);
-    hi[k].empty_cells = w[0]; hi[k].nonfinite_modes = w[1];
+    hi[k].empty_cells = w[0]; hi[k].nonfinite_modes = bis ? bad_modes[k] : w[1];
     for (int p = 0; p < P; p++) hi[k].max_cell = w[2 + p] > hi[k].max_cell ? w[2 + p] : hi[k].max_cell;
   }
-  memcpy(nmodes, hu.data(), nb * 8); memcpy(k2sum, hu.data() + nb, nb * 8);
+  if (bis) {
+    memcpy(bq->kmodes, kmodes.data(), (size_t)kb.nk * 8); memcpy(bq->ntri, ntri.data(), (size_t)nt * 8);
+    memcpy(bq->bsum, bsum.data(), bsum.size() * 8); memcpy(bq->psum, psum.data(), psum.size() * 8);
+  } else { memcpy(nmodes, hu.data(), nb * 8); memcpy(k2sum, hu.data() + nb, nb * 8); }
   memcpy(info, hi.data(), (size_t)nbins * sizeof(pf_halo_info));
   return 0;
 }
@@ -524,6 +590,20 @@ extern "C" int pf_halo_correlation(pf_ctx *c, int flags, size_t count, const dou
   pf_halo_info hinfo[PF_HALO_MAX_BINS];
   u64 bad_cells[PF_HALO_MAX_BINS];
   if (halo_spectra("pf_halo_correlation", HM_CORR, c, flags, count, pos, vel, scale, vfac, los, mass, nbins, mass_range, ncells, r2sum, xi, xi_cross, info ? hinfo : nullptr, bad_cells))
+    return 1;
+  for (int k = 0; k < nbins; k++) { info[k].halo = hinfo[k]; info[k].cells = hinfo[k].modes; info[k].nonfinite_cells = bad_cells[k]; }
+  return 0;
+}
+
+// info arrives as pf_bispec_info, handled as pf_halo_correlation handles its own.  kmodes, ntri and bsum ride where the body checks
+// for nulls; the body writes them through bq alone
+extern "C" int pf_halo_bispectrum(pf_ctx *c, int flags, size_t count, const double *pos, const double *vel, double scale, double vfac, int los, const int *mass, int nbins,
+                                  const int *mass_range, int kmin, int dk, int nk, unsigned long long *kmodes, double *ntri, double *bsum, double *psum, pf_bispec_info *info) {
+  pf_halo_info hinfo[PF_HALO_MAX_BINS];
+  u64 bad_cells[PF_HALO_MAX_BINS];
+  const HaloBispec bq = {kmin, dk, nk, kmodes, ntri, bsum, psum};
+  if (halo_spectra("pf_halo_bispectrum", HM_BISPEC, c, flags, count, pos, vel, scale, vfac, los, mass, nbins, mass_range, kmodes, (unsigned long long *)ntri, bsum, nullptr,
+                   info ? hinfo : nullptr, bad_cells, &bq))
     return 1;
   for (int k = 0; k < nbins; k++) { info[k].halo = hinfo[k]; info[k].cells = hinfo[k].modes; info[k].nonfinite_cells = bad_cells[k]; }
   return 0;

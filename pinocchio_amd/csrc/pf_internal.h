@@ -419,6 +419,26 @@ int pf_corr_form_device(const char *who, int task, int fb, const void *spec_m, c
 size_t pf_corr_shells_words(int n, int P);
 int pf_corr_shells_device(const char *who, int task, int fb, const void *real, int n, int x0, int nxl, long long pitch, int los, unsigned long long *words, pf_ctx *coll,
                           PfShellSums *sums, hipStream_t st);
+// ---- pf_bispec.hip: the bispectrum of a spectrum on the device (pf_halo.hip calls it; pf_bispec_core.h) ----
+#define PF_BISPEC_SLOTS 8   // copies of every counter of the passes: a workgroup adds to the copy of its index, one atomic per wave
+enum { PF_BISPEC_PH_TRANSFORM = 0, PF_BISPEC_PH_MASK, PF_BISPEC_PH_KEEP, PF_BISPEC_PH_TRIPLES };   // what `mark` is told has just run
+// this rank's ky-slab of the spectrum (rows of nzp complex) and x-slab of the real field (rows of rpitch reals)
+struct PfBispecGeom { int n, fb, y0, nyl, x0, nxl, rank, P; long long nzp, rpitch; };
+struct PfBispecBins { int kmin, dk, nk; };
+// on the host: sums [nt] = positive - negative; parts [2][nt] the positive sums, pair [nk], maxima [nk], kmodes [nk] (each may be null)
+struct PfBispecOut { double *sums, *parts, *pair, *maxima; unsigned long long *kmodes; unsigned long long nonfinite_modes, nonfinite_cells; };
+int pf_bispec_check_bins(const char *who, int task, int kmin, int dk, int nk, int n);   // the refusals of the k-bins (n 0: not 3 kmax > n)
+size_t pf_bispec_words(int kmin, int dk, int nk, int P);                                 // 64-bit words of tables a call needs
+// the mask pass of k-bin `bin` on the rows y0 .. y0 + nyl - 1: spec -> out (another field of the same layout), kind 0 the data field,
+// 1 the count field (spec null: nothing is read); counters: PF_BISPEC_SLOTS copies of (kmodes, modes that are not finite), cleared
+int pf_bispec_mask_device(const char *who, int task, int fb, const void *spec, void *out, int n, int y0, int nyl, long long pitch, const double *C, int kind, int kmin, int dk,
+                          int bin, unsigned long long *counters, hipStream_t st);
+// the whole estimator on a spectrum that stands in a field of its own (spec; null with kind 1: the count fields): per k-bin the mask
+// pass into `work` (the field of pf_ctx_matter_reverse_field), the context's reverse transform and the keep pass into store i of
+// `stores` (nk times nxl n^2 elements of the field type); then the triple pass (the pair pass with out->pair) and the sums on the
+// host, over the ranks of the context where it has several (collective).  words: pf_bispec_words of them.  Synchronises the stream
+int pf_bispec_device(const char *who, int task, pf_ctx *c, const PfBispecGeom &g, const PfBispecBins &kb, const void *spec, int kind, const double *C, void *work, void *stores,
+                     unsigned long long *words, void (*mark)(void *, int), void *user, PfBispecOut *out, hipStream_t st);
 // counters of a pf_matter call on the device: PF_MATTER_SLOTS copies of each, a workgroup adds to the copy of its index -- one counter for all
 // wavefronts of a 1024^3 call is 1.7e7 atomics on one address: the contrast pass took 778 ms that way and takes 8 (profiles/matter_notes.md);
 // the copies are summed (MC_MAX: reduced) on the host.  The scans of pf_matter_shells_device add to MC_NONFIN_MODES of `counters`
